@@ -20,7 +20,12 @@ Other BASELINE configs through the same timing contract: ``--model large`` (BERT
 gpt2-medium --zero-stage 3``.
 
 Rank 0 prints ONE JSON line; ``value`` = total tokens/s over all ranks, computed from the
-MAX step time over ranks.
+MAX step time over ranks; ``ms_per_step`` = that time per timed step (``--steps`` of them).
+
+A plain run sets up, warms up, times the steps and prints the line.  ``--dump-outputs DIR`` also
+writes the last timed step's loss and a seeded sample of the parameters it updated as ``.npy``
+files (same arguments, same inputs: two builds compare output for output).  ``--full`` is where
+any measurement beyond the headline figure belongs; none lives in this script today.
 """
 from __future__ import annotations
 
@@ -105,7 +110,35 @@ def parse():
     ap.add_argument("--reserve-gb", type=float, default=48.0, help="--prewarm reserve: bytes to reserve")
     ap.add_argument("--profile-steps", type=int, default=0)
     ap.add_argument("--no-tuned-gemms", action="store_true", help="skip the measured hipBLASLt solution table")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller as "
+                         "DIR/<name>.npy (float32): loss.npy, the step's loss, and params_sample.npy, a fixed "
+                         "seeded sample of every parameter as that step's update left it; the same arguments "
+                         "give the same inputs, so two builds can be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need (measurements beyond the timed steps); "
+                         "a plain run does only set-up, warm-up, the timed steps, --dump-outputs and the result "
+                         "line.  Today every such measurement lives in its own script (bench/, scripts/), so "
+                         "the option adds nothing yet")
     return ap.parse_args()
+
+
+DUMP_PER_TENSOR = 4096   # sampled elements per parameter (BERT-base: 338176 in all, 1.4 MB in float32)
+
+
+def _dump_outputs(out_dir: str, loss: torch.Tensor, named_params) -> None:
+    """Write the last timed step's results: the loss it returned and, per parameter (sorted by
+    name), DUMP_PER_TENSOR elements at indices drawn from a generator seeded with 0."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().cpu().numpy().reshape(1))
+    g = torch.Generator().manual_seed(0)
+    parts = []
+    for _, t in sorted(named_params, key=lambda nt: nt[0]):
+        flat = t.detach().reshape(-1)
+        idx = torch.randint(flat.numel(), (min(flat.numel(), DUMP_PER_TENSOR),), generator=g)
+        parts.append(flat[idx.to(flat.device)].float().cpu())
+    np.save(os.path.join(out_dir, "params_sample.npy"), torch.cat(parts).numpy())
 
 
 def _hand_gemm_config() -> dict:
@@ -287,6 +320,18 @@ def main():
         t = torch.tensor([dt], device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs:
+        if zero:
+            sd = engine.full_state_dict()   # collective under stage 3: every rank calls it
+            named = [(n, sd[n]) for n, _ in model.named_parameters()]
+        else:
+            if hasattr(opt, "synchronize"):
+                opt.synchronize()           # staged Adam chunks no forward has waited for yet
+            named = list(model.named_parameters())
+        if rank == 0:
+            _dump_outputs(args.dump_outputs, loss, named)
+    # args.full: measurements beyond the headline figure would run here, after the timed steps and
+    # the dump; there are none in this script yet
     tokens = world * B * S * args.steps
     value = tokens / dt
     if rank == 0:

@@ -1,9 +1,6 @@
 import os
 import sys
 
-# before anything initialises HIP (see distributed_training_and_deepspeed_amd/__init__.py)
-os.environ.setdefault("DEBUG_HIP_FORCE_GRAPH_QUEUES", "1")
-
 import pytest  # noqa: E402
 import torch  # noqa: E402
 

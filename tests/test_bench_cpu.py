@@ -24,6 +24,35 @@ def _run(port, *extra, nproc=2):
     return json.loads(lines[0])
 
 
+def _run_plain(*extra):
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--model", "tiny",
+           "--batch-size", "2", "--seq-len", "64", *extra]
+    out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600,
+                         env=dict(os.environ, OMP_NUM_THREADS="2"))
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def test_dump_outputs_repeatable_and_full_keeps_the_result_line(tmp_path):
+    """--dump-outputs writes the last timed step's loss and the seeded parameter sample as float32
+    .npy files, identical from run to run; --full leaves the headline fields as they are."""
+    import numpy as np
+    ra = _run_plain("--dump-outputs", str(tmp_path / "a"))
+    rb = _run_plain("--full", "--dump-outputs", str(tmp_path / "b"))
+    assert KEYS <= set(ra) and ra["steps"] == 2 and ra["warmup"] == 1 and ra["ms_per_step"] > 0
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "config"):
+        assert ra[k] == rb[k]
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["loss.npy", "params_sample.npy"]
+    for name in ("loss.npy", "params_sample.npy"):
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype == np.float32 and np.isfinite(a).all()
+        assert np.array_equal(a, b)
+    assert float(np.load(tmp_path / "a" / "loss.npy")[0]) == pytest.approx(ra["loss_last"], abs=1e-4)
+    assert np.load(tmp_path / "a" / "params_sample.npy").size > 1000
+
+
 @pytest.mark.parametrize("extra,engine", [(("--model", "tiny"), "DDP"),
                                           (("--model", "tiny", "--zero-stage", "2"), "ZeRO-2")])
 def test_bench_json_line_world2(free_port, extra, engine):

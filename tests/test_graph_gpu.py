@@ -168,10 +168,10 @@ def test_captured_step_with_rccl_collectives_matches_eager(engine):
 
     The cases run in THIS process, after the captured ZeRO tests above (each creating and
     destroying its own RCCL group): that sequence is the regression test of the round-5 crash, a
-    segfault in hipGraphLaunch on the first replay of the DDP graph.  Its cause was in the HIP
-    runtime's multi-queue graph replay (hip::Graph::UpdateStreams read past its parallel-stream
-    list when those streams shared the launch stream's hardware queue); the framework replays
-    graphs on one queue (DEBUG_HIP_FORCE_GRAPH_QUEUES=1, set at package import and in conftest.py).
+    segfault in hipGraphLaunch on the first replay of the DDP graph (hip::Graph::UpdateStreams
+    read past its parallel-stream list when those streams shared the launch stream's hardware
+    queue).  The graphs replay the way the HIP runtime replays them by default, with the hardware
+    queues the process was given (at least 4).
     DTD_RCCL_CAPTURE_INPROC=0 runs each case in a fresh process instead."""
     import os
     import subprocess
