@@ -79,9 +79,14 @@ def train(rank, world_size, batch_size, training_steps, bucket_size, model_name,
         if rank == 0:
             print(f"resumed from {opts.resume} (step {meta['step']})")
 
-    dataset = load_synthetic(cfg, batch_size * training_steps, seq_len=opts.seq_len, seed=0)
+    # --pad-fraction: that share of the rows is right-padded to a random length; --attention-mask:
+    # the rows' 0/1 mask goes to the model, whose attention then leaves the pad keys out (and the
+    # kernels skip their tiles) -- default off: pads attended to, as in the reference
+    dataset = load_synthetic(cfg, batch_size * training_steps, seq_len=opts.seq_len, seed=0,
+                             pad_fraction=opts.pad_fraction, return_attention_mask=opts.attention_mask)
     sampler = DistributedSampler(dataset, num_replicas=world_size, rank=rank)
-    loader = DeviceBatchLoader(dataset, batch_size=batch_size, sampler=sampler, device=device)
+    keys = ("input_ids", "labels") + (("attention_mask",) if opts.attention_mask else ())
+    loader = DeviceBatchLoader(dataset, batch_size=batch_size, sampler=sampler, device=device, keys=keys)
 
     progress = None
     if rank == 0 and not opts.quiet:
@@ -92,9 +97,12 @@ def train(rank, world_size, batch_size, training_steps, bucket_size, model_name,
             pass
     if opts.markers:
         enable_markers()
-    def step(input_ids, labels):
+    def step(input_ids, labels, attention_mask=None):
         with marker("forward"):
-            out = ddp(input_ids, labels=labels)
+            if attention_mask is None:
+                out = ddp(input_ids, labels=labels)
+            else:
+                out = ddp(input_ids, labels=labels, attention_mask=attention_mask)
         with marker("backward+allreduce"):
             out.loss.backward()
         with marker("optimizer"):
@@ -130,10 +138,11 @@ def train(rank, world_size, batch_size, training_steps, bucket_size, model_name,
     n = 0  # timed steps (graph warm-up steps trained before the clock started)
     for batch in batches:
         timer.start()
+        # (with --attention-mask the mask is the batch's third entry: a third static graph input)
         if graphed is not None and batch["input_ids"].shape == graphed.static["input_ids"].shape:
-            loss = graphed(input_ids=batch["input_ids"], labels=batch["labels"])
+            loss = graphed(**batch)
         else:
-            loss = step(batch["input_ids"], batch["labels"])
+            loss = step(**batch)
         timer.stop()
         n += 1
         if progress is not None:
@@ -177,6 +186,10 @@ if __name__ == "__main__":
     parser.add_argument("--resume", default="", help="checkpoint file to resume from")
     parser.add_argument("--opt-overlap", action="store_true",
                         help="stage the Adam update under the next forward (FusedAdam.overlap_with_forward)")
+    parser.add_argument("--attention-mask", action="store_true",
+                        help="pass the rows' attention_mask to the model: pad keys are not attended to")
+    parser.add_argument("--pad-fraction", type=float, default=0.0,
+                        help="share of the synthetic rows right-padded to a random length")
     parser.add_argument("--graph", nargs="?", const="on", default="auto", choices=["auto", "on", "off"],
                         help="capture the whole training step (bucket all-reduces included) in a hipGraph and "
                              "replay it (auto: on at <= 32 sequences per GPU, where the step is host-launch bound)")

@@ -7,7 +7,9 @@ unmasked labels -100 -- SURVEY.md D19) or causal labels = input_ids (pads includ
 There is no network on the MI355X boxes, so rows here are random token ids with the same
 shape, framing ([CLS] ... [SEP] for BERT) and the same masking law, generated
 deterministically from a seed.  ``pad_fraction`` optionally right-pads rows with the pad id
-to mimic short wikitext lines.
+to mimic short wikitext lines; ``return_attention_mask=True`` adds the matching 0/1
+``attention_mask`` column (ones over each row's drawn length), which the models turn into key
+ranges so the pads are not attended to.
 """
 from __future__ import annotations
 
@@ -38,6 +40,15 @@ def mlm_mask_tokens(input_ids: torch.Tensor, special_mask: torch.Tensor, vocab_s
 def synthetic_token_rows(n: int, seq_len: int, cfg: TransformerConfig, generator: torch.Generator,
                          pad_fraction: float = 0.0):
     """Random rows (+ special-token mask).  BERT rows are framed [CLS] x ... x [SEP]."""
+    ids, special, _ = synthetic_token_rows_lengths(n, seq_len, cfg, generator, pad_fraction)
+    return ids, special
+
+
+def synthetic_token_rows_lengths(n: int, seq_len: int, cfg: TransformerConfig, generator: torch.Generator,
+                                 pad_fraction: float = 0.0):
+    """``synthetic_token_rows`` plus each row's length before padding ([n] int64; ``seq_len`` for
+    an unpadded row).  Same draws from ``generator``, so the rows are the same."""
+    row_len = torch.full((n,), seq_len, dtype=torch.int64)
     specials = set(cfg.special_token_ids)
     lo = max(specials) + 1 if cfg.family == "bert" and specials else 0
     lo = min(lo, cfg.vocab_size - 1)
@@ -50,24 +61,32 @@ def synthetic_token_rows(n: int, seq_len: int, cfg: TransformerConfig, generator
         padded = torch.rand(n, generator=generator) < pad_fraction
         for i in torch.nonzero(padded).flatten().tolist():
             L = int(lengths[i])
+            row_len[i] = L
             if cfg.family == "bert":
                 ids[i, L - 1] = 102
-            ids[i, L:] = cfg.pad_token_id
+            # (a shrunken-vocabulary preset may keep its family's pad id: stay inside the table)
+            ids[i, L:] = cfg.pad_token_id if cfg.pad_token_id < cfg.vocab_size else 0
     special = torch.zeros_like(ids, dtype=torch.bool)
     for s in specials:
         special |= ids == s
-    return ids, special
+    return ids, special, row_len
 
 
 class SyntheticLMDataset(Dataset):
-    """Map-style dataset of {'input_ids', 'labels'} rows, statically masked like util.py."""
+    """Map-style dataset of {'input_ids', 'labels'} rows, statically masked like util.py.
+    ``return_attention_mask=True`` adds an 'attention_mask' column: a prefix of ones of each row's
+    drawn length (not ``ids != pad``: a random token can equal the pad id)."""
+
+    attention_mask = None   # [n, seq_len] int64 0/1 when requested
 
     def __init__(self, cfg: TransformerConfig, num_samples: int, seq_len: int = 512, mlm: bool | None = None,
-                 seed: int = 0, pad_fraction: float = 0.0):
+                 seed: int = 0, pad_fraction: float = 0.0, return_attention_mask: bool = False):
         self.cfg = cfg
         self.mlm = (cfg.family == "bert") if mlm is None else mlm
         g = torch.Generator().manual_seed(seed)
-        ids, special = synthetic_token_rows(num_samples, seq_len, cfg, g, pad_fraction)
+        ids, special, row_len = synthetic_token_rows_lengths(num_samples, seq_len, cfg, g, pad_fraction)
+        if return_attention_mask:
+            self.attention_mask = (torch.arange(seq_len).view(1, -1) < row_len.view(-1, 1)).to(torch.int64)
         if self.mlm:
             self.input_ids, self.labels = mlm_mask_tokens(ids, special, cfg.vocab_size, cfg.mask_token_id, g)
         else:
@@ -77,7 +96,10 @@ class SyntheticLMDataset(Dataset):
         return self.input_ids.shape[0]
 
     def __getitem__(self, i):
-        return {"input_ids": self.input_ids[i], "labels": self.labels[i]}
+        row = {"input_ids": self.input_ids[i], "labels": self.labels[i]}
+        if self.attention_mask is not None:
+            row["attention_mask"] = self.attention_mask[i]
+        return row
 
     def select(self, indices) -> "SyntheticLMDataset":
         """HF ``Dataset.select`` parity (data_parallel_training.py:36)."""
@@ -85,13 +107,15 @@ class SyntheticLMDataset(Dataset):
         out = object.__new__(SyntheticLMDataset)
         out.cfg, out.mlm = self.cfg, self.mlm
         out.input_ids, out.labels = self.input_ids[idx], self.labels[idx]
+        out.attention_mask = None if self.attention_mask is None else self.attention_mask[idx]
         return out
 
 
 def load_synthetic(cfg: TransformerConfig, num_samples: int, seq_len: int = 512, mlm: bool | None = None,
-                   seed: int = 0) -> SyntheticLMDataset:
+                   seed: int = 0, pad_fraction: float = 0.0, return_attention_mask: bool = False) -> SyntheticLMDataset:
     """Stand-in for ``util.load_wikitext`` (same columns, same masking law)."""
-    return SyntheticLMDataset(cfg, num_samples, seq_len, mlm=mlm, seed=seed)
+    return SyntheticLMDataset(cfg, num_samples, seq_len, mlm=mlm, seed=seed, pad_fraction=pad_fraction,
+                              return_attention_mask=return_attention_mask)
 
 
 class NativeSyntheticLM:

@@ -4,7 +4,8 @@ Reference (util.py:38-60): load wikitext-2-v1 train, batch-tok
 ``padding='max_length', truncation=True, return_special_tokens_mask=True``, then either apply
 *static* MLM masking once (``collator.torch_mask_tokens``: 15% / 80-10-10) or, for causal LMs,
 ``labels = input_ids`` -- pads included, because the collator is bypassed (quirk 8) -- and keep
-no attention mask.
+no attention mask.  ``return_attention_mask=True`` keeps the tokenizer's ``attention_mask`` as a
+third column (the models' ``attention_mask=`` argument; default off = the reference's behaviour).
 
 There is no network on the MI355X boxes, so this loader reads a LOCAL copy: a directory saved with
 ``datasets.Dataset.save_to_disk`` / ``DatasetDict.save_to_disk`` (split ``train``, column ``text``),
@@ -50,15 +51,19 @@ def read_text_lines(path: str, split: str = "train", column: str = "text") -> li
 class TokenizedLMDataset(SyntheticLMDataset):
     """Same container as the synthetic datasets ({'input_ids', 'labels'} rows, ``select``)."""
 
-    def __init__(self, input_ids: torch.Tensor, labels: torch.Tensor, mlm: bool, cfg=None):  # noqa: D107
+    def __init__(self, input_ids: torch.Tensor, labels: torch.Tensor, mlm: bool, cfg=None,
+                 attention_mask: torch.Tensor | None = None):  # noqa: D107
         self.cfg, self.mlm = cfg, mlm
         self.input_ids, self.labels = input_ids, labels
+        self.attention_mask = attention_mask
 
 
 def load_wikitext(tokenizer, collator=None, max_length: int | None = None, *, path: str, mlm: bool | None = None,
-                  mlm_probability: float | None = None, seed: int = 0, limit: int | None = None) -> TokenizedLMDataset:
+                  mlm_probability: float | None = None, seed: int = 0, limit: int | None = None,
+                  return_attention_mask: bool = False) -> TokenizedLMDataset:
     """``util.load_wikitext`` parity on a local corpus.  ``collator`` (optional) supplies
-    ``mlm`` / ``mlm_probability`` like HF's DataCollatorForLanguageModeling."""
+    ``mlm`` / ``mlm_probability`` like HF's DataCollatorForLanguageModeling.
+    ``return_attention_mask``: keep the tokenizer's 0/1 ``attention_mask`` as a dataset column."""
     if mlm is None:
         mlm = bool(getattr(collator, "mlm", True))
     if mlm_probability is None:
@@ -68,7 +73,8 @@ def load_wikitext(tokenizer, collator=None, max_length: int | None = None, *, pa
         lines = lines[:limit]
     max_length = max_length or getattr(tokenizer, "model_max_length", 512)
     enc = tokenizer(lines, padding="max_length", truncation=True, max_length=max_length,
-                    return_special_tokens_mask=True, return_tensors="pt")
+                    return_special_tokens_mask=True, return_tensors="pt",
+                    **({"return_attention_mask": True} if return_attention_mask else {}))
     ids = enc["input_ids"].to(torch.int64)
     if mlm:
         special = enc["special_tokens_mask"].bool()
@@ -76,4 +82,5 @@ def load_wikitext(tokenizer, collator=None, max_length: int | None = None, *, pa
         inputs, labels = mlm_mask_tokens(ids, special, len(tokenizer), tokenizer.mask_token_id, g, mlm_probability)
     else:
         inputs, labels = ids, ids.clone()          # util.py:54-58: pads included, no attention mask
-    return TokenizedLMDataset(inputs, labels, mlm)
+    amask = enc["attention_mask"].to(torch.int64) if return_attention_mask else None
+    return TokenizedLMDataset(inputs, labels, mlm, attention_mask=amask)

@@ -5,8 +5,11 @@ Reference usage: ``BertForMaskedLM.from_pretrained('bert-base-cased'|'bert-large
 per SURVEY.md D15: word+position+token-type embeddings -> LN(1e-12) -> dropout 0.1;
 N post-LN encoder layers (fused q/k/v projection: identical parameter count to HF's three
 Linears); MLM head dense -> GELU(erf) -> LN -> decoder tied to the word embeddings + bias;
-cross entropy with ignore_index -100 over all labelled positions.  No attention mask is
-applied (the reference never passes one), and there is no pooler (add_pooling_layer=False).
+cross entropy with ignore_index -100 over all labelled positions.  By default no attention mask
+is applied (the reference never passes one, so pads are attended to); ``forward(...,
+attention_mask=...)`` takes HF's 0/1 ``[B, S]`` key-padding mask of a left- or right-padded batch
+(contiguous masks only, ``ops.attention.key_range_from_mask``).  Position ids stay ``arange(S)``,
+which equals HF's for right-padded batches.  There is no pooler (add_pooling_layer=False).
 Parameter count for bert-base-cased: 108,340,804.
 """
 from __future__ import annotations
@@ -18,6 +21,7 @@ from torch import nn
 
 from .config import BERT_BASE, TransformerConfig, get_config
 from .layers import Embeddings, MLMHead
+from ..ops.attention import key_range_from_mask
 from .transformer import Runtime, TransformerLayer, prefetch_masks, stage_dgrad_transposes
 
 
@@ -48,18 +52,20 @@ class BertForMaskedLM(nn.Module):
         """Parameters shared between units (tied decoder / word embeddings)."""
         return [self.embeddings.word] if self.head.decoder_w is None else []
 
-    def encode(self, input_ids: torch.Tensor) -> torch.Tensor:
+    def encode(self, input_ids: torch.Tensor, attention_mask: torch.Tensor | None = None) -> torch.Tensor:
         if input_ids.is_cuda and self.training:
             prefetch_masks(self.layers, input_ids)
+        # one conversion per forward (on the device, no host sync); every layer gets the ranges
+        key_range = key_range_from_mask(attention_mask) if attention_mask is not None else None
         x = self.embeddings(input_ids)
         for layer in self.layers:
-            x = layer(x)
+            x = layer(x) if key_range is None else layer(x, key_range=key_range)
         stage_dgrad_transposes(self.layers, x)
         return x
 
     def forward(self, input_ids: torch.Tensor, labels: torch.Tensor | None = None,
-                return_logits: bool = False) -> MaskedLMOutput:
-        x = self.encode(input_ids)
+                return_logits: bool = False, attention_mask: torch.Tensor | None = None) -> MaskedLMOutput:
+        x = self.encode(input_ids, attention_mask)
         out = MaskedLMOutput()
         if labels is not None:
             out.loss = self.head(x, labels)

@@ -9,6 +9,12 @@ gpt2-medium.  SURVEY.md D17:
   * OPT: word + learned positions (offset 2), pre-LN, ReLU, final LN, tied head;
   * GPT-2: wte + wpe, pre-LN, tanh-GELU, final LN, tied head.
 Loss: shifted next-token cross entropy (labels = input_ids, ignore_index -100).
+
+``forward(..., attention_mask=...)`` takes HF's 0/1 ``[B, S]`` key-padding mask (contiguous: left-
+or right-padded, ``ops.attention.key_range_from_mask``); without it pads are attended to, as in the
+reference.  Position ids stay ``arange(S)``: equal to HF's for right-padded batches, and for BLOOM
+(ALiBi, no position table) under either padding side.  For a LEFT-padded OPT or GPT-2 batch HF
+derives the positions from the mask (first real token = position 0); here they are not shifted.
 """
 from __future__ import annotations
 
@@ -19,6 +25,7 @@ from torch import nn
 
 from .config import BLOOM_560M, TransformerConfig, get_config
 from .layers import Embeddings, LayerNorm, LMHead
+from ..ops.attention import key_range_from_mask
 from .transformer import Runtime, TransformerLayer, prefetch_masks, stage_dgrad_transposes
 
 
@@ -50,20 +57,22 @@ class CausalLM(nn.Module):
         """Parameters shared between units (LM head tied to the word embeddings)."""
         return [self.embeddings.word]
 
-    def encode(self, input_ids: torch.Tensor) -> torch.Tensor:
+    def encode(self, input_ids: torch.Tensor, attention_mask: torch.Tensor | None = None) -> torch.Tensor:
         if input_ids.is_cuda and self.training:
             prefetch_masks(self.layers, input_ids)
+        # one conversion per forward (on the device, no host sync); every layer gets the ranges
+        key_range = key_range_from_mask(attention_mask) if attention_mask is not None else None
         x = self.embeddings(input_ids)
         for layer in self.layers:
-            x = layer(x)
+            x = layer(x) if key_range is None else layer(x, key_range=key_range)
         stage_dgrad_transposes(self.layers, x)
         if self.final_ln is not None:
             x = self.final_ln(x)
         return x
 
     def forward(self, input_ids: torch.Tensor, labels: torch.Tensor | None = None,
-                return_logits: bool = False) -> CausalLMOutput:
-        x = self.encode(input_ids)
+                return_logits: bool = False, attention_mask: torch.Tensor | None = None) -> CausalLMOutput:
+        x = self.encode(input_ids, attention_mask)
         out = CausalLMOutput()
         if labels is not None:
             out.loss = self.head(x, labels)

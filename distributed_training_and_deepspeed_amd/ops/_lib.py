@@ -65,8 +65,12 @@ _SIGS = {
     # attention.hip
     "dtd_attn_fwd": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, F, P, U32, P]),
     "dtd_attn_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, F, P, P]),
+    # (the _range forms: the same arguments, then the int32 [B][2] key ranges before the stream)
+    "dtd_attn_fwd_range": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, F, P, U32, P, P]),
+    "dtd_attn_bwd_range": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, F, P, P, P]),
     "dtd_attn_masks": (I, [P, I, I, I, F, P, U32, P]),
     "dtd_attn_set_bwd_form": (I, [I]),
+    "dtd_attn_set_bwd_kernels": (I, [I]),
     "dtd_attn_fused_bwd_built": (I, []),
     # attention_f32.hip
     "dtd_attn_fwd_f32": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, F, P]),

@@ -6,11 +6,18 @@ output ``ctx`` is ``[B*S, H*D]`` and the log-sum-exp ``lse`` is ``[B, H, S]`` fp
 log of sum(exp(score)), score = q.k * scale + bias).  Supported score modifiers: causal mask,
 ALiBi (BLOOM: bias = slope_h * key_position, which equals BLOOM's relative form up to a
 per-row constant that softmax cancels) and dropout on the probabilities with the counter RNG
-(mask element index = ((b*H + h)*S + i)*S + j, regenerated in backward).
+(mask element index = ((b*H + h)*S + i)*S + j, regenerated in backward), and a per-sequence key
+range ``key_range`` (int32 ``[B, 2]`` = (lo, hi), the key-padding mask of a left- or right-padded
+batch, ``key_range_from_mask``): key j of sequence b takes part iff lo <= j < hi, before and
+independently of the causal mask and ALiBi.  Padded *query* rows are computed like any other (they
+attend to the valid keys, as in HF models).  A row left without a key -- lo >= hi, or causal with
+q < lo -- has ctx = 0, lse = -inf and contributes nothing to any gradient.  Dropout keep bits stay
+indexed by the absolute (b, h, q, key), so a range does not change which bits a pair draws.
 
 Reference semantics: HF BertSelfAttention eager path (matmul, softmax, dropout, matmul --
 SURVEY.md K2, reference model/transformer.py:80-86); the reference never passes an
-attention mask for BERT (data_parallel_training.py:53), so padding is attended to.
+attention mask for BERT (data_parallel_training.py:53), so by default (no ``key_range``) padding
+is attended to.
 """
 from __future__ import annotations
 
@@ -47,7 +54,44 @@ def _cdt(t: torch.Tensor) -> torch.dtype:
     return torch.float64 if t.dtype == torch.float64 else torch.float32
 
 
-def _scores(q, k, scale, causal, slopes):
+def key_range_from_mask(attention_mask: torch.Tensor, check: bool = False) -> torch.Tensor:
+    """(lo, hi) key ranges, int32 ``[B, 2]`` on the mask's device, of a 0/1 ``[B, S]`` attention
+    mask: lo = first kept position, hi = last kept position + 1 -- left padding, right padding or
+    both; a row of zeros gives (0, 0).  Runs on the device with no host synchronisation, so a
+    captured step can call it on its static mask input.
+
+    Only contiguous masks are supported: a mask with holes inside [lo, hi) is treated as if the
+    holes were kept.  ``check=True`` synchronises and raises ``ValueError`` for such a mask."""
+    if attention_mask.dim() != 2:
+        raise ValueError(f"attention_mask must be [B, S], got {tuple(attention_mask.shape)}")
+    B, S = attention_mask.shape
+    if S == 0:
+        return torch.zeros((B, 2), dtype=torch.int32, device=attention_mask.device)
+    keep = attention_mask != 0
+    idx = torch.arange(S, device=keep.device, dtype=torch.int32)
+    hi = torch.where(keep, idx + 1, torch.zeros_like(idx)).amax(1)
+    lo = torch.minimum(torch.where(keep, idx, torch.full_like(idx, S)).amin(1), hi)
+    if check and bool((keep.sum(1) != hi - lo).any()):
+        raise ValueError("attention_mask has holes inside its kept range: only contiguous "
+                         "(left- / right-padded) masks map to a key range")
+    return torch.stack([lo, hi], 1).contiguous()
+
+
+def _range_mask(key_range, B, S, device):
+    """[B, 1, 1, S] bool, True where the key is OUTSIDE its sequence's range."""
+    kr = key_range.to(device=device, dtype=torch.int64).view(B, 2)
+    j = torch.arange(S, device=device).view(1, S)
+    return ((j < kr[:, :1]) | (j >= kr[:, 1:])).view(B, 1, 1, S)
+
+
+def _probs(s, lse):
+    """exp(s - lse) with the empty-row rule: a row without a key has lse = -inf (and s = -inf
+    throughout), where exp(s - lse) would be NaN -- its probabilities are 0."""
+    lse = lse[..., None].to(s.dtype)
+    return torch.exp(s - lse.masked_fill(lse == float("-inf"), 0.0))
+
+
+def _scores(q, k, scale, causal, slopes, key_range=None):
     c = _cdt(q)
     s = torch.matmul(q.to(c), k.to(c).transpose(-1, -2)) * scale
     S = q.shape[2]
@@ -56,6 +100,8 @@ def _scores(q, k, scale, causal, slopes):
     if causal:
         m = torch.ones(S, S, dtype=torch.bool, device=s.device).triu(1)
         s = s.masked_fill(m, float("-inf"))
+    if key_range is not None:
+        s = s.masked_fill(_range_mask(key_range, q.shape[0], S, s.device), float("-inf"))
     return s
 
 
@@ -65,23 +111,24 @@ def _drop_mask(B, H, S, p, rng, sid, device):
 
 
 def attn_fwd_ref(qkv, B, S, H, D, causal=False, slopes=None, p=0.0, rng: RngState | None = None, sid=0,
-                 scale=None):
+                 scale=None, key_range=None):
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     q, k, v = _split(qkv, B, S, H, D)
-    s = _scores(q, k, scale, causal, slopes)
-    lse = torch.logsumexp(s, -1)
-    prob = torch.exp(s - lse[..., None])
+    s = _scores(q, k, scale, causal, slopes, key_range)
+    lse = torch.logsumexp(s, -1)       # -inf for a row without a key
+    prob = _probs(s, lse)
     if p > 0:
         prob = prob * _drop_mask(B, H, S, p, rng, sid, qkv.device) / (1.0 - p)
     ctx = torch.matmul(prob, v.to(prob.dtype))  # [B,H,S,D]
     return ctx.transpose(1, 2).reshape(B * S, H * D).to(qkv.dtype), lse
 
 
-def attn_bwd_ref(dctx, qkv, ctx, lse, B, S, H, D, causal=False, slopes=None, p=0.0, rng=None, sid=0, scale=None):
+def attn_bwd_ref(dctx, qkv, ctx, lse, B, S, H, D, causal=False, slopes=None, p=0.0, rng=None, sid=0, scale=None,
+                 key_range=None):
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     q, k, v = _split(qkv, B, S, H, D)
-    s = _scores(q, k, scale, causal, slopes)
-    prob = torch.exp(s - lse[..., None].to(s.dtype))
+    s = _scores(q, k, scale, causal, slopes, key_range)
+    prob = _probs(s, lse)
     c = s.dtype
     do = dctx.view(B, S, H, D).transpose(1, 2).to(c)
     o = ctx.view(B, S, H, D).transpose(1, 2).to(c)
@@ -124,14 +171,33 @@ def set_bwd_form(form: str) -> str:
     return _BWD_FORMS[old]
 
 
+def set_bwd_kernels(dq: bool = True, dkdv: bool = True) -> tuple[bool, bool]:
+    """Timing hook (scripts/bench_attn.py): run only the dQ or only the dK/dV kernel of the split
+    backward, to price them separately.  Anything but (True, True) leaves part of dqkv unwritten.
+    Returns the previous setting."""
+    old = _lib.lib().dtd_attn_set_bwd_kernels(int(dq) | (int(dkdv) << 1))
+    return bool(old & 1), bool(old & 2)
+
+
 def fused_bwd_built() -> bool:
     """The one-kernel backward forms are compiled only into experimental builds
     (DTD_BUILD_EXPERIMENTAL=1): they measured no faster than the split kernels."""
     return _lib.has("dtd_attn_fused_bwd_built") and bool(_lib.lib().dtd_attn_fused_bwd_built())
 
 
-def fused_bwd_applies(S: int, D: int, causal: bool, slopes) -> bool:
-    return D == 64 and not causal and slopes is None and S % 128 == 0 and S <= 512 and fused_bwd_built()
+def fused_bwd_applies(S: int, D: int, causal: bool, slopes, key_range=None) -> bool:
+    """Whether ``attn_bwd`` may take a one-kernel form; never with a key range (split pair only)."""
+    return (key_range is None and D == 64 and not causal and slopes is None and S % 128 == 0 and S <= 512
+            and fused_bwd_built())
+
+
+def _range_arg(key_range: torch.Tensor, B: int, device) -> torch.Tensor:
+    """The kernels' kv_range argument: int32 [B, 2], contiguous, on the activations' device."""
+    if tuple(key_range.shape) != (B, 2):
+        raise ValueError(f"key_range must be [B, 2] = [{B}, 2], got {tuple(key_range.shape)}")
+    if not _lib.has("dtd_attn_fwd_range"):
+        raise _lib.KernelError("the kernel library has no ranged attention entry points (stale build)")
+    return key_range.to(device=device, dtype=torch.int32).contiguous()
 
 
 def kernel_supported(qkv: torch.Tensor, D: int) -> bool:
@@ -231,16 +297,25 @@ def attn_masks_async(B, S, H, D, p, rng: RngState, sid, device) -> PendingMasks 
 
 
 def attn_fwd(qkv, B, S, H, D, causal=False, slopes=None, p=0.0, rng: RngState | None = None, sid=0,
-             masks: PendingMasks | None = None):
+             masks: PendingMasks | None = None, key_range: torch.Tensor | None = None):
     """Returns (ctx [B*S, H*D], lse [B, H, S] fp32, masks).  ``masks`` holds the dropout keep
     bits for the backward ([2, B*H*S*ceil(S/32)] int32 on the kernel path, None otherwise);
-    pass the ``attn_masks_async`` result to reuse masks generated ahead on a side stream."""
+    pass the ``attn_masks_async`` result to reuse masks generated ahead on a side stream.
+
+    ``key_range``: optional int32 [B, 2] per-sequence key ranges (module docstring).  The bf16
+    kernels skip the key tiles outside a range.  fp32 inputs with a range take the math reference
+    (the reference-precision fp32 kernels know no range)."""
+    if key_range is not None and qkv.dtype == torch.float32:
+        if masks is not None:    # keep bits generated ahead for the fp32 kernels: unused, but join
+            torch.cuda.current_stream(qkv.device).wait_event(masks.event)   # before their buffer is freed
+        ctx, lse = attn_fwd_ref(qkv, B, S, H, D, causal, slopes, p, rng, sid, key_range=key_range)
+        return ctx, lse, None
     if f32_kernel_supported(qkv, D):
         return _attn_fwd_f32(qkv, B, S, H, D, causal, slopes, p, rng, sid, masks)
     if not kernel_supported(qkv, D):
         if qkv.is_cuda and qkv.dtype == torch.bfloat16 and _lib.has("dtd_attn_fwd") is False:
             _warn_once()
-        ctx, lse = attn_fwd_ref(qkv, B, S, H, D, causal, slopes, p, rng, sid)
+        ctx, lse = attn_fwd_ref(qkv, B, S, H, D, causal, slopes, p, rng, sid, key_range=key_range)
         return ctx, lse, None
     qkv = qkv.contiguous()
     ctx = torch.empty((B * S, H * D), dtype=qkv.dtype, device=qkv.device)
@@ -258,25 +333,39 @@ def attn_fwd(qkv, B, S, H, D, causal=False, slopes=None, p=0.0, rng: RngState | 
     ld = 3 * H * D
     base = qkv.data_ptr()
     es = qkv.element_size()
-    _lib.call("dtd_attn_fwd", base, base + H * D * es, base + 2 * H * D * es, ctx.data_ptr(), lse.data_ptr(),
-              _lib.ptr(sl), _lib.ptr(masks), B, S, H, D, ld, H * D, int(causal), 1.0 / math.sqrt(D), float(p),
-              rng_ptr, sid, _lib.stream())
+    args = (base, base + H * D * es, base + 2 * H * D * es, ctx.data_ptr(), lse.data_ptr(),
+            _lib.ptr(sl), _lib.ptr(masks), B, S, H, D, ld, H * D, int(causal), 1.0 / math.sqrt(D), float(p),
+            rng_ptr, sid)
+    if key_range is None:
+        _lib.call("dtd_attn_fwd", *args, _lib.stream())
+    else:
+        kr = _range_arg(key_range, B, qkv.device)
+        _lib.call("dtd_attn_fwd_range", *args, kr.data_ptr(), _lib.stream())
     return ctx, lse, masks
 
 
 def attn_bwd(dctx, qkv, ctx, lse, B, S, H, D, causal=False, slopes=None, p=0.0, rng=None, sid=0, masks=None,
-             dbias=None):
+             dbias=None, key_range: torch.Tensor | None = None):
     """Returns dqkv [B*S, 3*H*D] in the qkv layout.  ``dbias`` = (dst, acc): also writes the
     column sums of dqkv (the qkv projection's bias gradient) -- on the kernel path as per-wave
-    partials from the dQ / dK,dV epilogues (no extra pass over dqkv)."""
+    partials from the dQ / dK,dV epilogues (no extra pass over dqkv).
+
+    ``key_range``: the forward's ranges.  Keys outside a range get zero dK / dV; the bf16 path
+    runs the split dQ + dK/dV kernels (never a one-kernel form) and skips the key tiles / key
+    blocks outside the range.  fp32 inputs with a range take the math reference."""
     from . import functional as Fx
+    if key_range is not None and qkv.dtype == torch.float32:
+        dqkv = attn_bwd_ref(dctx, qkv, ctx, lse, B, S, H, D, causal, slopes, p, rng, sid, key_range=key_range)
+        if dbias is not None:
+            Fx.bias_grad(dqkv, *dbias)
+        return dqkv
     if f32_kernel_supported(qkv, D) and (p <= 0 or masks is not None):
         dqkv = _attn_bwd_f32(dctx, qkv, ctx, lse, B, S, H, D, causal, slopes, p, masks)
         if dbias is not None:
             Fx.bias_grad(dqkv, *dbias)
         return dqkv
     if not kernel_supported(qkv, D):
-        dqkv = attn_bwd_ref(dctx, qkv, ctx, lse, B, S, H, D, causal, slopes, p, rng, sid)
+        dqkv = attn_bwd_ref(dctx, qkv, ctx, lse, B, S, H, D, causal, slopes, p, rng, sid, key_range=key_range)
         if dbias is not None:
             Fx.bias_grad(dqkv, *dbias)
         return dqkv
@@ -291,10 +380,14 @@ def attn_bwd(dctx, qkv, ctx, lse, B, S, H, D, causal=False, slopes=None, p=0.0, 
     if dbias is not None and D == 64:
         # one row per (batch, 32-row block of a 128-row workgroup tile); every entry is written
         part = torch.empty((B * 4 * ((S + 127) // 128), ld), dtype=torch.float32, device=qkv.device)
-    _lib.call("dtd_attn_bwd", qb, qb + H * D * es, qb + 2 * H * D * es, ctx.data_ptr(), dctx.data_ptr(),
-              lse.data_ptr(), delta.data_ptr(), _lib.ptr(masks), gb, gb + H * D * es, gb + 2 * H * D * es,
-              _lib.ptr(sl), B, S, H, D, ld, H * D, int(causal), 1.0 / math.sqrt(D), float(p), _lib.ptr(part),
-              _lib.stream())
+    args = (qb, qb + H * D * es, qb + 2 * H * D * es, ctx.data_ptr(), dctx.data_ptr(),
+            lse.data_ptr(), delta.data_ptr(), _lib.ptr(masks), gb, gb + H * D * es, gb + 2 * H * D * es,
+            _lib.ptr(sl), B, S, H, D, ld, H * D, int(causal), 1.0 / math.sqrt(D), float(p), _lib.ptr(part))
+    if key_range is None:
+        _lib.call("dtd_attn_bwd", *args, _lib.stream())
+    else:
+        kr = _range_arg(key_range, B, qkv.device)
+        _lib.call("dtd_attn_bwd_range", *args, kr.data_ptr(), _lib.stream())
     if dbias is not None:
         if part is not None:
             dst, acc = dbias

@@ -28,7 +28,9 @@
 //
 // Features: causal mask, ALiBi (bias = slope_h * key), attention-probability dropout with the
 // counter RNG (mask index ((b*H+h)*S + q)*S + key, regenerated in backward), arbitrary S
-// (bounds-masked), head_dim 64 or 128.  q/k/v/o are strided views (row stride `ld`) into the
+// (bounds-masked), head_dim 64 or 128, and an optional key range [lo, hi) per sequence (the
+// key-padding mask of a padded batch: keys outside it score -inf and their tiles are skipped --
+// the RANGE instantiations, reached through dtd_attn_fwd_range / dtd_attn_bwd_range only).  q/k/v/o are strided views (row stride `ld`) into the
 // fused [B*S, 3*H*D] projection output, so no transpose/copy kernels are needed.
 #include <stdio.h>
 #include <type_traits>
@@ -175,7 +177,15 @@ struct FwdArgs {
   const uint32_t* maskB;  // [B*H][W][Sp]: bit j of word (w, key) = query 32w+j
   int B, S, H, ld, ldo, causal, W;
   float scale, p, thr;
+  const int* kv_range;    // optional [B][2] = (lo, hi): key j of sequence b takes part iff lo <= j < hi (RANGE kernels)
 };
+
+// Key range of sequence b, clamped to [0, S]; b is workgroup-uniform, so both are scalar loads and
+// every loop bound derived from them stays wave-uniform.
+__device__ __forceinline__ void load_range(const int* kv_range, int b, int S, int& lo, int& hi) {
+  lo = __builtin_amdgcn_readfirstlane(min(max(kv_range[2 * b], 0), S));
+  hi = __builtin_amdgcn_readfirstlane(max(min(kv_range[2 * b + 1], S), 0));
+}
 
 // Dropout keep-masks for one attention call, generated once in a VALU-only pass at full
 // occupancy (instead of re-hashing inside the MFMA-bound forward, dK/dV and dQ kernels) and
@@ -281,6 +291,31 @@ __device__ __forceinline__ void xcd_tile(int& tx, int& ty) {
   ty = T / nx;
 }
 
+// xcd_tile for the ranged dK/dV kernel, whose workgroups outside a sequence's key range return at
+// once.  In xcd_tile's order the key blocks of a head are adjacent, so with a uniform range every
+// nx-th workgroup of an XCD works and the rest exit: measured at B·H = 3072, S = 512, one or two
+// working blocks of four took as long as all four (645 vs 692 us, against 116 us with none) --
+// consistent with workgroups being dealt to the CUs in turn, the working ones always to the same
+// quarter of them.  Here each XCD's tiles are reordered in groups of kGroup heads, block index
+// outermost inside a group: working and returning workgroups come in runs of kGroup, which reach
+// every CU, while the blocks of one head stay within kGroup * nx workgroups of each other (their
+// Q / dO tiles still meet in the XCD's L2).  A bijection on the tiles for any grid.
+__device__ __forceinline__ void xcd_tile_grouped(int& tx, int& ty) {
+  constexpr int kGroup = 32;
+  const int nx = gridDim.x, n = nx * gridDim.y;
+  const int L = blockIdx.x + nx * blockIdx.y;
+  if (n % 8) { tx = blockIdx.x; ty = blockIdx.y; return; }
+  const int per = n / 8, gs = kGroup * nx;
+  int i = L / 8;                           // position inside this XCD's chunk of `per` tiles
+  if (i < (per / gs) * gs) {               // full groups only; the tail keeps xcd_tile's order
+    const int r = i % gs;
+    i = (i - r) + (r % kGroup) * nx + r / kGroup;
+  }
+  const int T = (L % 8) * per + i;
+  tx = T % nx;
+  ty = T / nx;
+}
+
 // Bounded buffer resource (base readfirstlane'd into SGPRs): loads at byte offsets >= `bytes`
 // return 0 without touching memory, which is how the tile loads below handle rows past S and
 // absent dropout masks (bytes = 0) with no per-lane clamp or select.
@@ -368,7 +403,10 @@ struct TileLoader {
 // double-buffered in LDS, fed by a 2-deep register ring of global loads: one barrier per tile.
 // PK: the exp-argument FMAs and the row-sum adds as packed fp32 (v_pk_fma_f32 / v_pk_add_f32, two
 // scores per issue) -- 32 fewer VALU issues per 64-key tile; the row sum's add order differs.
-template <int D, int OCC, int BN, int RING, bool PK = false>
+// RANGE: per-sequence key range a.kv_range (key-padding mask): keys outside [lo, hi) score -inf
+// and only the key tiles floor(lo / BN) .. ceil(min(hi, causal end) / BN) - 1 are visited.  A row
+// left without a key (lo >= hi, or causal with q < lo) ends with m = -inf, l = 0: ctx 0, lse -inf.
+template <int D, int OCC, int BN, int RING, bool PK = false, bool RANGE = false>
 __global__ void __launch_bounds__(256, OCC) attn_fwd_kernel(FwdArgs a) {
   // K rows (ds_read_b128, 4x16-lane groups): pitch D+8 puts the 16 rows of a group on 16
   // distinct 4-bank windows.  V (ds_read_b64_tr_b16, rows rr = 0..3 x column halves g = 0,1 per
@@ -413,8 +451,15 @@ __global__ void __launch_bounds__(256, OCC) attn_fwd_kernel(FwdArgs a) {
   for (int d = 0; d < NDB; ++d) oacc[d] = f32x16{};
   float m = -INFINITY, l = 0.f;
 
-  const int kend = a.causal ? min(S, qblk + 128) : S;
+  // key range of this sequence (RANGE): (0, S) otherwise; khi replaces S as the end of the keys
+  int klo = 0, khi = S;
+  if constexpr (RANGE) load_range(a.kv_range, b, S, klo, khi);
+  const int kend = a.causal ? min(khi, qblk + 128) : khi;
   const int nt = (kend + BN - 1) / BN;
+  // first tile of the range; with no tile to run (t0 >= nt) the loop below is skipped and the
+  // epilogue writes the empty rows.  `last` clamps the ring's look-ahead loads to a tile >= t0.
+  const int t0 = RANGE ? klo / BN : 0;
+  const int last = RANGE ? max(nt - 1, t0) : nt - 1;
   // K/V tiles stream through a 2-deep register ring: tile t+2's global loads are issued while
   // tile t is computed and written to LDS only at the end of tile t+1, so each load has two
   // tiles of compute to arrive (one tile of MFMA/softmax work is shorter than an HBM round trip).
@@ -430,23 +475,23 @@ __global__ void __launch_bounds__(256, OCC) attn_fwd_kernel(FwdArgs a) {
     asm volatile("" :: "v"(out));   // retire the previous prefetch held in this register
     out = __builtin_amdgcn_raw_buffer_load_b32(mrs, lane * 4, k0 * 4, 0);
   };
-  kl0.load(ksrc, 0);
-  vl0.load(vsrc, 0);
+  kl0.load(ksrc, t0 * BN);
+  vl0.load(vsrc, t0 * BN);
   kl0.store(Ks[0], KP);
   vl0.store(Vs[0], VP);
   {
-    const int k1 = min(1, nt - 1) * BN, k2 = min(2, nt - 1) * BN;
+    const int k1 = min(t0 + 1, last) * BN, k2 = min(t0 + 2, last) * BN;
     kl1.load(ksrc, k1); vl1.load(vsrc, k1); prefetch_words(k1, pf1);
     if constexpr (RING == 2) { kl0.load(ksrc, k2); vl0.load(vsrc, k2); prefetch_words(k2, pf0); }
   }
   __syncthreads();
-  // SET = register set holding tile t+1 (t even -> 1, t odd -> 0)
+  // SET = register set holding tile t+1 (t - t0 even -> 1, odd -> 0)
   auto tile = [&](auto set_c, int t) {
     constexpr int SET = decltype(set_c)::value;
     TileLoader<D, BN>& kn = SET ? kl1 : kl0;
     TileLoader<D, BN>& vn = SET ? vl1 : vl0;
     uint32_t& pfn = SET ? pf1 : pf0;
-    const int buf = t & 1, k0 = t * BN;
+    const int buf = (t - t0) & 1, k0 = t * BN;
     const bf16* K = Ks[buf];
     const bf16* V = Vs[buf];
     // keep masks of the tile's first 32-key block: issued ahead of the score MFMAs (their L2
@@ -473,7 +518,8 @@ __global__ void __launch_bounds__(256, OCC) attn_fwd_kernel(FwdArgs a) {
     // log2-domain scores.  Fast path (no ALiBi, interior tile): the row max is taken on the raw
     // accumulator (scale > 0) and the scale is folded into the exponent's FMA -- 4 VALU per score
     // incl. the running sum, vs 10+ with a per-element scale/bias/mask pass.
-    const bool needmask = (k0 + BN > S) || (a.causal && k0 + BN - 1 > q0);
+    // (RANGE: khi <= S stands for the end of the keys, and the tile holding klo is masked too)
+    const bool needmask = (k0 + BN > khi) || (RANGE && k0 < klo) || (a.causal && k0 + BN - 1 > q0);
     const bool slow = needmask || sl2 != 0.f;
     float tmax = -INFINITY;
     if (slow) {
@@ -483,7 +529,7 @@ __global__ void __launch_bounds__(256, OCC) attn_fwd_kernel(FwdArgs a) {
         for (int i = 0; i < 16; ++i) {
           const int key = k0 + kb * 32 + crow(i, hh);
           float s = fmaf(sacc[kb][i], sc2, sl2 * (float)key);
-          if (needmask && (key >= S || (a.causal && key > q))) s = -INFINITY;
+          if (needmask && (key >= khi || (RANGE && key < klo) || (a.causal && key > q))) s = -INFINITY;
           sacc[kb][i] = s;
           tmax = fmaxf(tmax, s);
         }
@@ -498,6 +544,8 @@ __global__ void __launch_bounds__(256, OCC) attn_fwd_kernel(FwdArgs a) {
     // defer-max (wave-uniform decision): keep the running max unless some row's tile max
     // exceeds it by > kRescaleThr; the previous tile's P.V is complete, so O and l are the
     // only terms at the old scale.  m = -inf (first tile / fully masked so far) -> alpha 0.
+    // (A row with every key masked so far has tmax = m = -inf: the NaN difference takes the
+    // rescale, which leaves m = -inf, l = 0, O = 0.)
     if (!__all(tmax - m <= a.thr)) {
       const float mnew = fmaxf(m, tmax);
       const float alpha = m == -INFINITY ? 0.f : fexp2(m - mnew);
@@ -567,7 +615,7 @@ __global__ void __launch_bounds__(256, OCC) attn_fwd_kernel(FwdArgs a) {
     }
     __syncthreads();
   };
-  for (int t = 0; t < nt; t += 2) {
+  for (int t = t0; t < nt; t += 2) {
     tile(std::integral_constant<int, 1>{}, t);
     if (t + 1 < nt) tile(std::integral_constant<int, 0>{}, t + 1);
   }
@@ -584,6 +632,7 @@ __global__ void __launch_bounds__(256, OCC) attn_fwd_kernel(FwdArgs a) {
       for (int t = 0; t < 4; ++t) v4[t] = (bf16)(oacc[d][4 * gq + t] * inv_l);
       *reinterpret_cast<bf16x4*>(op + d * 32 + 8 * gq + 4 * hh) = v4;
     }
+  // (a row without a key: m = -inf, l = 0 -> -inf)
   if (hh == 0) a.lse[(size_t)bh * S + q] = (m + log2f(l)) * kLn2;
 }
 
@@ -776,6 +825,7 @@ struct BwdArgs {
   // optional [B * 4 * ceil(S/128)][3 H D] fp32 column partials of dqkv (the qkv bias gradient):
   // one row per (batch, 32-row block of a wave), finished by colsum_finalize
   float* bias_part;
+  const int* kv_range;    // optional [B][2] key range per sequence (see FwdArgs; RANGE kernels only)
 };
 
 // Column sums of a wave's 32 rows x 64 columns of dQ / dK / dV, straight from the accumulators
@@ -818,8 +868,13 @@ __device__ __forceinline__ int colsum_col(int k, int hh) { return (k >> 4) * 32 
 // multiple of 128).  The runtime `needmask` branch alone is not enough: hipcc hoists the 16 key /
 // query comparisons and their lane-mask combines above it, 48 VALU + 52 SALU per 32-query
 // sub-block executed on every interior block.
-template <int D, int OCC, int BM, bool DROP, bool ALIBI, bool MASK = true>
+// RANGE (needs MASK): key range per sequence.  A workgroup whose 128 keys lie wholly outside
+// [lo, hi) runs no query tile and writes zero dK / dV rows and zero bias partials (the gradient
+// buffer is uninitialised); otherwise keys outside the range are masked like keys past S.  Padded
+// query rows take part like any other; a row without a key (lse = -inf) has P = 0.
+template <int D, int OCC, int BM, bool DROP, bool ALIBI, bool MASK = true, bool RANGE = false>
 __global__ void __launch_bounds__(256, OCC) attn_bwd_dkdv_kernel(BwdArgs a) {
+  static_assert(MASK || !RANGE, "a key range needs the masked form");
   constexpr bool SWZ = D == 64;                 // swizzled unpadded image (swz64_off)
   constexpr int QP = SWZ ? D : D + 8, NC = D / 16, NDB = D / 32;
   // One LDS block, row statistics first: placed after the 72 KiB of Q/dO tiles (BM = 128) their
@@ -838,12 +893,35 @@ __global__ void __launch_bounds__(256, OCC) attn_bwd_dkdv_kernel(BwdArgs a) {
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), hh = lane >> 5,
             r = lane & 31;
   int tx, ty;
-  xcd_tile(tx, ty);
+  if constexpr (RANGE) xcd_tile_grouped(tx, ty);
+  else xcd_tile(tx, ty);
   const int bh = ty, b = bh / a.H, h = bh % a.H;
   const int S = a.S;
   const int kblk = tx * 128;
   const int key = kblk + w * 32 + r;
   const bool kvalid = key < S;
+  int klo = 0, khi = S;
+  if constexpr (RANGE) {
+    load_range(a.kv_range, b, S, klo, khi);
+    if (kblk >= khi || kblk + 128 <= klo) {   // block-uniform: no key of this block is in the range
+      if (a.bias_part && D == 64) {
+        float* row = a.bias_part + ((size_t)b * gridDim.x * 4 + (kblk >> 5) + w) * (3 * a.H * D) + h * D + colsum_col(r, hh);
+        row[a.H * D] = 0.f;
+        row[2 * a.H * D] = 0.f;
+      }
+      if (kvalid) {
+        bf16* dkp = a.dk + (size_t)(b * S + key) * a.ld + h * D;
+        bf16* dvp = a.dv + (size_t)(b * S + key) * a.ld + h * D;
+#pragma unroll
+        for (int c = 0; c < D / 8; ++c) {   // both half-waves hold lane r's key: 4 of 8 columns each
+          *reinterpret_cast<bf16x4*>(dkp + 8 * c + 4 * hh) = bf16x4{};
+          *reinterpret_cast<bf16x4*>(dvp + 8 * c + 4 * hh) = bf16x4{};
+        }
+      }
+      return;
+    }
+  }
+  const bool kin = key >= klo && key < khi;     // this lane's key takes part (RANGE)
   const float sl2 = a.slopes ? a.slopes[h] * kLog2e : 0.f;
   const float sc2 = a.scale * kLog2e;
   constexpr bool drop = DROP;
@@ -880,6 +958,8 @@ __global__ void __launch_bounds__(256, OCC) attn_bwd_dkdv_kernel(BwdArgs a) {
     if (threadIdx.x < BM) {
       const int qq = q0 + threadIdx.x;
       lse_r = qq < S ? -lseb[qq] * kLog2e : 0.f;   // stored negated: P = 2^fma(s, sc2, -lse)
+      // a row without a key (lse = -inf): P = 2^(s - inf) = 0, not 2^(s + inf)
+      if constexpr (RANGE) lse_r = lse_r == INFINITY ? -INFINITY : lse_r;
       // dS = P (dP - delta); with dropout the kernel forms dS' = (1 - p) dS = Pm dP - P (1 - p) delta
       // (Pm = P * keep), so delta is stored pre-scaled and dK takes the 1 / (1 - p) at the end
       del_r = qq < S ? -delb[qq] * (DROP ? 1.f - a.p : 1.f) : 0.f;
@@ -931,7 +1011,8 @@ __global__ void __launch_bounds__(256, OCC) attn_bwd_dkdv_kernel(BwdArgs a) {
       }
       const int qrow0 = q0 + qb * 32;
       // block-uniform predicate (a scalar branch, never a per-element one)
-      const bool needmask = MASK && ((kblk + 128 > S) || (qrow0 + 32 > S) || (a.causal && kblk + 127 > qrow0));
+      bool needmask = MASK && ((kblk + 128 > S) || (qrow0 + 32 > S) || (a.causal && kblk + 127 > qrow0));
+      if constexpr (RANGE) needmask = needmask || kblk + 128 > khi || kblk < klo;   // the blocks holding lo / hi
       // this query block's keep masks (after the S / dP MFMAs consumed their LDS operands)
       uint64_t mk[16];
       if constexpr (DROP) {
@@ -961,7 +1042,8 @@ __global__ void __launch_bounds__(256, OCC) attn_bwd_dkdv_kernel(BwdArgs a) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           const int qq = qrow0 + crow(i, hh);
-          const bool ok = kvalid && qq < S && !(a.causal && key > qq);
+          bool ok = kvalid && qq < S && !(a.causal && key > qq);
+          if constexpr (RANGE) ok = ok && kin;
           sacc[i] = ok ? sacc[i] : 0.f;
         }
       }
@@ -1042,7 +1124,9 @@ __global__ void __launch_bounds__(256, OCC) attn_bwd_dkdv_kernel(BwdArgs a) {
 // forward); recomputes S^T and dP^T per 64-key tile and accumulates dQ^T = K^T.dS^T in
 // registers -- no atomics, no cross-workgroup reduction.
 // PK: packed-fp32 exp arguments and dS = P (dP - delta) (v_pk_fma_f32 / v_pk_mul_f32)
-template <int D, int OCC, int BN, int RING, bool PK = false>
+// RANGE: key range per sequence, same tile range and masks as the forward (attn_fwd_kernel); a
+// row without a key (lse = -inf) gets P = 0 on every tile, so dQ = 0.
+template <int D, int OCC, int BN, int RING, bool PK = false, bool RANGE = false>
 __global__ void __launch_bounds__(256, OCC) attn_bwd_dq_kernel(BwdArgs a) {
   constexpr bool SWZ = D == 64;                 // swizzled unpadded K / V images (swz64_off)
   constexpr int KP = SWZ ? D : D + 8, NC = D / 16, NDB = D / 32;
@@ -1079,7 +1163,10 @@ __global__ void __launch_bounds__(256, OCC) attn_bwd_dq_kernel(BwdArgs a) {
       of[c] = qvalid ? *reinterpret_cast<const bf16x8*>(op + 16 * c + 8 * hh) : bf16x8{};
     }
   }
-  const float lse2 = qvalid ? a.lse[(size_t)bh * S + q] * kLog2e : 0.f;
+  float lse2 = qvalid ? a.lse[(size_t)bh * S + q] * kLog2e : 0.f;
+  // a row without a key: every key it meets is masked below (P = 0 by select); +inf here also
+  // makes the unmasked exponent 2^(s - inf) = 0 instead of 2^(s + inf)
+  if constexpr (RANGE) lse2 = lse2 == -INFINITY ? INFINITY : lse2;
   // delta = rowsum(dO * O) of this lane's query, from the dO fragments already in registers and
   // one O row read (no separate delta pass re-reading dO); stored for the dK/dV kernel, which
   // runs after this one
@@ -1100,8 +1187,13 @@ __global__ void __launch_bounds__(256, OCC) attn_bwd_dq_kernel(BwdArgs a) {
 #pragma unroll
   for (int d = 0; d < NDB; ++d) dq[d] = f32x16{};
 
-  const int kend = a.causal ? min(S, qblk + 128) : S;
+  // key range, first tile and look-ahead clamp as in attn_fwd_kernel
+  int klo = 0, khi = S;
+  if constexpr (RANGE) load_range(a.kv_range, b, S, klo, khi);
+  const int kend = a.causal ? min(khi, qblk + 128) : khi;
   const int nt = (kend + BN - 1) / BN;
+  const int t0 = RANGE ? klo / BN : 0;
+  const int last = RANGE ? max(nt - 1, t0) : nt - 1;
   // K/V tiles + dropout keep words through a 2-deep register ring (see attn_fwd_kernel)
   constexpr int NKB = BN / 32;
   // RING = 1: one register set in flight (fewer VGPRs -> 3 waves per SIMD), see attn_fwd_kernel
@@ -1114,12 +1206,12 @@ __global__ void __launch_bounds__(256, OCC) attn_bwd_dq_kernel(BwdArgs a) {
     asm volatile("" :: "v"(out));
     out = __builtin_amdgcn_raw_buffer_load_b32(mrs, lane * 4, k0 * 4, 0);
   };
-  kl0.load(ksrc, 0);
-  vl0.load(vsrc, 0);
+  kl0.load(ksrc, t0 * BN);
+  vl0.load(vsrc, t0 * BN);
   kl0.store_bwd(Ks[0], KP);
   vl0.store_bwd(Vs[0], KP);
   {
-    const int k1 = min(1, nt - 1) * BN, k2 = min(2, nt - 1) * BN;
+    const int k1 = min(t0 + 1, last) * BN, k2 = min(t0 + 2, last) * BN;
     kl1.load(ksrc, k1); vl1.load(vsrc, k1); prefetch_words(k1, pf1);
     if constexpr (RING == 2) { kl0.load(ksrc, k2); vl0.load(vsrc, k2); prefetch_words(k2, pf0); }
   }
@@ -1129,10 +1221,10 @@ __global__ void __launch_bounds__(256, OCC) attn_bwd_dq_kernel(BwdArgs a) {
     TileLoader<D, BN>& kn = SET ? kl1 : kl0;
     TileLoader<D, BN>& vn = SET ? vl1 : vl0;
     uint32_t& pfn = SET ? pf1 : pf0;
-    const int buf = t & 1, k0 = t * BN;
+    const int buf = (t - t0) & 1, k0 = t * BN;
     const bf16* K = Ks[buf];
     const bf16* V = Vs[buf];
-    const bool needmask = !qvalid || (k0 + BN > S) || (a.causal && k0 + BN - 1 > q0);
+    const bool needmask = !qvalid || (k0 + BN > khi) || (RANGE && k0 < klo) || (a.causal && k0 + BN - 1 > q0);
 #pragma unroll
     for (int kb = 0; kb < BN / 32; ++kb) {
       f32x16 sacc = f32x16{}, pacc = f32x16{};
@@ -1159,7 +1251,7 @@ __global__ void __launch_bounds__(256, OCC) attn_bwd_dq_kernel(BwdArgs a) {
         for (int i = 0; i < 16; ++i) {
           const int key = k0 + kb * 32 + crow(i, hh);
           float pv = fexp2(fmaf(sacc[i], sc2, sl2 * (float)key - lse2));
-          if (needmask && (!qvalid || key >= S || (a.causal && key > q))) pv = 0.f;
+          if (needmask && (!qvalid || key >= khi || (RANGE && key < klo) || (a.causal && key > q))) pv = 0.f;
           sacc[i] = pv;
         }
       } else if constexpr (PK) {
@@ -1215,7 +1307,7 @@ __global__ void __launch_bounds__(256, OCC) attn_bwd_dq_kernel(BwdArgs a) {
     }
     __syncthreads();
   };
-  for (int t = 0; t < nt; t += 2) {
+  for (int t = t0; t < nt; t += 2) {
     tile(std::integral_constant<int, 1>{}, t);
     if (t + 1 < nt) tile(std::integral_constant<int, 0>{}, t + 1);
   }
@@ -1852,9 +1944,11 @@ static bool offsets_fit(int S, int ld, int ldo) {
   return (long long)S * ld * 2 < lim && (long long)S * ldo * 2 < lim && 32 * W * W * 4 < lim;
 }
 
-DTD_EXPORT int dtd_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const float* slopes,
-                            uint32_t* masks, int B, int S, int H, int D, int ld, int ldo, int causal, float scale,
-                            float p, const uint64_t* rng, uint32_t sid, hipStream_t s) {
+// kv_range: nullptr, or device int32 [B][2] = (lo, hi) key range per sequence (key-padding mask);
+// the ranged call always takes attn_fwd_kernel's RANGE form (no pipe / packed-fp32 variants).
+static int attn_fwd_launch(const void* q, const void* k, const void* v, void* o, float* lse, const float* slopes,
+                           uint32_t* masks, int B, int S, int H, int D, int ld, int ldo, int causal, float scale,
+                           float p, const uint64_t* rng, uint32_t sid, const int* kv_range, hipStream_t s) {
   if (B * S * H == 0) return 0;
   if (!offsets_fit(S, ld, ldo)) return (int)hipErrorInvalidValue;
   const int W = (S + 31) / 32;
@@ -1874,9 +1968,13 @@ DTD_EXPORT int dtd_attn_fwd(const void* q, const void* k, const void* v, void* o
   const float thr = thr_env ? (float)atof(thr_env) : kRescaleThr;
   const uint32_t* mBk = mA ? mA + (size_t)B * H * (32 * W) * W : nullptr;
   FwdArgs a{(const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, lse, slopes, mA, mBk, B, S, H, ld, ldo, causal, W,
-            scale, p, thr};
+            scale, p, thr, kv_range};
   dim3 grid((S + 127) / 128, B * H);
-  if (D == 64 && fwd_pipe()) {
+  if (kv_range) {
+    if (D == 64) hipLaunchKernelGGL((attn_fwd_kernel<64, 3, 64, 1, false, true>), grid, dim3(256), 0, s, a);
+    else if (D == 128) hipLaunchKernelGGL((attn_fwd_kernel<128, 1, 64, 2, false, true>), grid, dim3(256), 0, s, a);
+    else return (int)hipErrorInvalidValue;
+  } else if (D == 64 && fwd_pipe()) {
     // two score tiles live: 198 VGPRs, 2 waves / SIMD (at 3 it spills)
     hipLaunchKernelGGL((attn_fwd_pipe_kernel<64, 2, 64>), grid, dim3(256), 0, s, a);
   } else if (D == 64) {
@@ -1891,6 +1989,21 @@ DTD_EXPORT int dtd_attn_fwd(const void* q, const void* k, const void* v, void* o
     return (int)hipErrorInvalidValue;
   }
   DTD_LAUNCH_CHECK();
+}
+
+DTD_EXPORT int dtd_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const float* slopes,
+                            uint32_t* masks, int B, int S, int H, int D, int ld, int ldo, int causal, float scale,
+                            float p, const uint64_t* rng, uint32_t sid, hipStream_t s) {
+  return attn_fwd_launch(q, k, v, o, lse, slopes, masks, B, S, H, D, ld, ldo, causal, scale, p, rng, sid, nullptr, s);
+}
+
+// dtd_attn_fwd with a per-sequence key range (kv_range: device int32 [B][2], required)
+DTD_EXPORT int dtd_attn_fwd_range(const void* q, const void* k, const void* v, void* o, float* lse,
+                                  const float* slopes, uint32_t* masks, int B, int S, int H, int D, int ld, int ldo,
+                                  int causal, float scale, float p, const uint64_t* rng, uint32_t sid,
+                                  const int* kv_range, hipStream_t s) {
+  if (!kv_range) return (int)hipErrorInvalidValue;
+  return attn_fwd_launch(q, k, v, o, lse, slopes, masks, B, S, H, D, ld, ldo, causal, scale, p, rng, sid, kv_range, s);
 }
 
 // 0 = the dQ + dK/dV pair, 1 = fused where it applies, 2 = fused, 4-wave form; returns the previous
@@ -1928,11 +2041,34 @@ static void launch_dkdv(dim3 grid, hipStream_t s, const BwdArgs& a) {
   else hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, OCC, BM, false, false>), grid, dim3(256), 0, s, a);
 }
 
+// With a key range: always the masked form -- the blocks holding lo / hi need it even where
+// launch_dkdv would pick MASK = false.
+template <int D, int OCC, int BM>
+static void launch_dkdv_range(dim3 grid, hipStream_t s, const BwdArgs& a) {
+  const bool drop = a.maskB != nullptr, alibi = a.slopes != nullptr;
+  if (drop && alibi) hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, OCC, BM, true, true, true, true>), grid, dim3(256), 0, s, a);
+  else if (drop) hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, OCC, BM, true, false, true, true>), grid, dim3(256), 0, s, a);
+  else if (alibi) hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, OCC, BM, false, true, true, true>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, OCC, BM, false, false, true, true>), grid, dim3(256), 0, s, a);
+}
+
+// Which kernels of the split backward run (bit 0: dQ, bit 1: dK/dV): a timing hook for
+// scripts/bench_attn.py, which prices the two kernels separately.  Anything but 3 leaves part of
+// the gradient unwritten (and dK/dV alone reads a delta the skipped dQ kernel did not write).
+static int g_bwd_kernels = 3;
+DTD_EXPORT int dtd_attn_set_bwd_kernels(int mask) {
+  const int old = g_bwd_kernels;
+  g_bwd_kernels = mask & 3;
+  return old;
+}
+
 // dq/dk/dv: bf16 views with row stride ld into dqkv.  `delta` is [B,H,S] fp32 scratch.
-DTD_EXPORT int dtd_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout,
-                            const float* lse, float* delta, const uint32_t* masks, void* dq, void* dk, void* dv,
-                            const float* slopes, int B, int S, int H, int D, int ld, int ldo, int causal, float scale,
-                            float p, float* bias_part, hipStream_t s) {
+// kv_range: nullptr, or device int32 [B][2] key range per sequence; the ranged call always runs
+// the split dQ + dK/dV pair in its default tile forms.
+static int attn_bwd_launch(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                           const float* lse, float* delta, const uint32_t* masks, void* dq, void* dk, void* dv,
+                           const float* slopes, int B, int S, int H, int D, int ld, int ldo, int causal, float scale,
+                           float p, float* bias_part, const int* kv_range, hipStream_t s) {
   if (B * S * H == 0) return 0;
   if (D != 64 && D != 128) return (int)hipErrorInvalidValue;
   if (!offsets_fit(S, ld, ldo)) return (int)hipErrorInvalidValue;
@@ -1943,7 +2079,18 @@ DTD_EXPORT int dtd_attn_bwd(const void* q, const void* k, const void* v, const v
   dim3 grid((S + 127) / 128, B * H);
   BwdArgs a{(const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)dout, lse, delta, (const bf16*)o,
             (bf16*)dq, (bf16*)dk, (bf16*)dv, slopes, mA, mB, B, S, H, ld, ldo, causal, W, scale, p,
-            D == 64 ? bias_part : nullptr};
+            D == 64 ? bias_part : nullptr, kv_range};
+  const bool run_dq = g_bwd_kernels & 1, run_dkdv = g_bwd_kernels & 2;
+  if (kv_range) {
+    if (D == 64) {
+      if (run_dq) hipLaunchKernelGGL((attn_bwd_dq_kernel<64, 3, 64, 1, false, true>), grid, dim3(256), 0, s, a);
+      if (run_dkdv) launch_dkdv_range<64, 2, 128>(grid, s, a);
+    } else {
+      if (run_dq) hipLaunchKernelGGL((attn_bwd_dq_kernel<128, 1, 64, 2, false, true>), grid, dim3(256), 0, s, a);
+      if (run_dkdv) launch_dkdv_range<128, 1, 64>(grid, s, a);
+    }
+    DTD_LAUNCH_CHECK();
+  }
 #if DTD_ATTN_FUSED_BWD
   if (D == 64 && !causal && !slopes && S % 128 == 0 && S <= 512 && bwd_fused()) {
     const bool drop = mA != nullptr;
@@ -1971,7 +2118,8 @@ DTD_EXPORT int dtd_attn_bwd(const void* q, const void* k, const void* v, const v
   // dQ first: it also produces delta = rowsum(dO * O), which the dK/dV kernel then reads
   if (D == 64) {
     const int o = occupancy(2);
-    if (tile_keys(1) == 128) hipLaunchKernelGGL((attn_bwd_dq_kernel<64, 2, 128, 2>), grid, dim3(256), 0, s, a);
+    if (!run_dq) {}
+    else if (tile_keys(1) == 128) hipLaunchKernelGGL((attn_bwd_dq_kernel<64, 2, 128, 2>), grid, dim3(256), 0, s, a);
     else if (o >= 3 && fwd_pk()) hipLaunchKernelGGL((attn_bwd_dq_kernel<64, 3, 64, 1, true>), grid, dim3(256), 0, s, a);
     else if (o >= 3) hipLaunchKernelGGL((attn_bwd_dq_kernel<64, 3, 64, 1>), grid, dim3(256), 0, s, a);
     else if (o == 2) hipLaunchKernelGGL((attn_bwd_dq_kernel<64, 2, 64, 2>), grid, dim3(256), 0, s, a);
@@ -1979,13 +2127,32 @@ DTD_EXPORT int dtd_attn_bwd(const void* q, const void* k, const void* v, const v
     // query tile of the dK/dV loop: 128 rows halves the barriers / exposed load latency per
     // query row at 2 blocks per CU (75 KB LDS each); DTD_ATTN_DKDV_BM=64 selects the old tile
     const int bm = getenv("DTD_ATTN_DKDV_BM") ? atoi(getenv("DTD_ATTN_DKDV_BM")) : 128;
-    if (bm == 128 && occupancy(1) == 1) launch_dkdv<64, 1, 128>(grid, s, a);
+    if (!run_dkdv) {}
+    else if (bm == 128 && occupancy(1) == 1) launch_dkdv<64, 1, 128>(grid, s, a);
     else if (bm == 128) launch_dkdv<64, 2, 128>(grid, s, a);
     else if (occupancy(1) >= 2) launch_dkdv<64, 2, 64>(grid, s, a);
     else launch_dkdv<64, 1, 64>(grid, s, a);
   } else {
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<128, 1, 64, 2>), grid, dim3(256), 0, s, a);
-    launch_dkdv<128, 1, 64>(grid, s, a);
+    if (run_dq) hipLaunchKernelGGL((attn_bwd_dq_kernel<128, 1, 64, 2>), grid, dim3(256), 0, s, a);
+    if (run_dkdv) launch_dkdv<128, 1, 64>(grid, s, a);
   }
   DTD_LAUNCH_CHECK();
+}
+
+DTD_EXPORT int dtd_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                            const float* lse, float* delta, const uint32_t* masks, void* dq, void* dk, void* dv,
+                            const float* slopes, int B, int S, int H, int D, int ld, int ldo, int causal, float scale,
+                            float p, float* bias_part, hipStream_t s) {
+  return attn_bwd_launch(q, k, v, o, dout, lse, delta, masks, dq, dk, dv, slopes, B, S, H, D, ld, ldo, causal, scale,
+                         p, bias_part, nullptr, s);
+}
+
+// dtd_attn_bwd with a per-sequence key range (kv_range: device int32 [B][2], required)
+DTD_EXPORT int dtd_attn_bwd_range(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                                  const float* lse, float* delta, const uint32_t* masks, void* dq, void* dk, void* dv,
+                                  const float* slopes, int B, int S, int H, int D, int ld, int ldo, int causal,
+                                  float scale, float p, float* bias_part, const int* kv_range, hipStream_t s) {
+  if (!kv_range) return (int)hipErrorInvalidValue;
+  return attn_bwd_launch(q, k, v, o, dout, lse, delta, masks, dq, dk, dv, slopes, B, S, H, D, ld, ldo, causal, scale,
+                         p, bias_part, kv_range, s);
 }

@@ -5,14 +5,24 @@ variants (DTD_ATTN_OCC="fwd,dkdv,dq" waves/SIMD).  Prints one JSON line per vari
 fwd_us: forward kernel with the dropout keep bits generated ahead (as in the model, where the
 mask kernel runs on a side stream under the forward GEMMs); mask_us: the mask generator alone;
 bwd_us: dK/dV + dQ, or the one-kernel fused backward for a variant named "fused" (or "fused:<occ>").
-Env: B, H, P, CAUSAL=1 (model FLOPs are quoted for the full square).  """
+Env: B, H, P, CAUSAL=1 (model FLOPs are quoted for the full square).
+
+``--valid-frac F [F ...]``: the key-range (key-padding mask) kernels instead -- every row gets the
+right-padded range (0, round(F * S)).  One JSON line per fraction with the forward, dQ, dK/dV and
+whole-backward times (dq_us / dkdv_us: each kernel alone, ops.attention.set_bwd_kernels), plus a
+line ``"valid_frac": null`` for the call without a range.  The configurations are timed
+interleaved, ``--rounds`` times over; each figure is the median of its rounds (the spread is in
+``*_minmax``).  ``--out FILE`` appends the lines to a jsonl file, ``--tag`` labels them."""
+import argparse
 import json
 import os
+import statistics
 import sys
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from distributed_training_and_deepspeed_amd.ops import _lib  # noqa: E402
 from distributed_training_and_deepspeed_amd.ops import attention as A  # noqa: E402
 from distributed_training_and_deepspeed_amd.ops.rng import RngState  # noqa: E402
 
@@ -30,7 +40,60 @@ def timeit(fn, iters=20):
     return e0.elapsed_time(e1) / iters * 1e3
 
 
+def ranged(args, B, S, H, D, p, causal, qkv, dctx, rng):
+    """Forward / dQ / dK/dV times per valid fraction (None = no range), interleaved over rounds.
+    With a kernel library from before the key ranges (DTD_KERNELS_SO=<older build>, the yardstick
+    of an A/B) only the call without a range is timed, forward and whole backward."""
+    has_range = _lib.has("dtd_attn_fwd_range") and _lib.has("dtd_attn_set_bwd_kernels")
+    configs = [None] + (list(args.valid_frac) if has_range else [])
+    pend = A.attn_masks_async(B, S, H, D, p, rng, 3, qkv.device) if p > 0 else None
+    torch.cuda.synchronize()
+    state = {}
+    for f in configs:
+        kr = None if f is None else torch.tensor([[0, int(round(f * S))]] * B, dtype=torch.int32, device="cuda")
+        ctx, lse, mk = A.attn_fwd(qkv, B, S, H, D, causal, None, p, rng, 3, masks=pend, key_range=kr)
+        state[f] = (kr, ctx, lse, mk)
+    times = {f: {"fwd_us": [], "dq_us": [], "dkdv_us": [], "bwd_us": []} for f in configs}
+    for _ in range(args.rounds):
+        for f in configs:
+            kr, ctx, lse, mk = state[f]
+            t = times[f]
+            t["fwd_us"].append(timeit(lambda: A.attn_fwd(qkv, B, S, H, D, causal, None, p, rng, 3, masks=pend, key_range=kr)))
+            bwd = lambda: A.attn_bwd(dctx, qkv, ctx, lse, B, S, H, D, causal, None, p, rng, 3, mk, key_range=kr)  # noqa: E731
+            t["bwd_us"].append(timeit(bwd))
+            if not has_range:
+                continue
+            try:     # (dK/dV alone reads an unwritten delta: wrong values, same work)
+                A.set_bwd_kernels(dq=True, dkdv=False)
+                t["dq_us"].append(timeit(bwd))
+                A.set_bwd_kernels(dq=False, dkdv=True)
+                t["dkdv_us"].append(timeit(bwd))
+            finally:
+                A.set_bwd_kernels(True, True)
+    for f in configs:
+        rec = {"tag": args.tag, "valid_frac": f, "B": B, "S": S, "H": H, "D": D, "causal": causal, "p": p,
+               "rounds": args.rounds}
+        for k, v in times[f].items():
+            if not v:
+                continue
+            rec[k] = round(statistics.median(v), 1)
+            rec[k + "_minmax"] = [round(min(v), 1), round(max(v), 1)]
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as fh:
+                fh.write(line + "\n")
+
+
 def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("occ", nargs="*", help='occupancy variants "fwd,dkdv,dq", "fused" or "fused:<occ>"')
+    ap.add_argument("--valid-frac", type=float, nargs="+", default=None,
+                    help="time the key-range kernels at these valid fractions of S (right-padded rows)")
+    ap.add_argument("--rounds", type=int, default=5, help="--valid-frac: interleaved rounds per configuration")
+    ap.add_argument("--out", default="", help="--valid-frac: append the JSON lines to this file")
+    ap.add_argument("--tag", default="", help="--valid-frac: label of the records")
+    args = ap.parse_args()
     B, S, H, D = int(os.environ.get("B", 32)), int(os.environ.get("S", 512)), int(os.environ.get("H", 12)), 64
     p = float(os.environ.get("P", 0.1))
     causal = os.environ.get("CAUSAL", "0") == "1"
@@ -42,7 +105,10 @@ def main():
     for _ in range(50):
         A.attn_fwd(qkv, B, S, H, D, causal, None, p, rng, 3)
     torch.cuda.synchronize()
-    for occ in sys.argv[1:] or ["1,1,1", "2,2,2", "3,2,2", "3,2,3"]:
+    if args.valid_frac is not None:
+        ranged(args, B, S, H, D, p, causal, qkv, dctx, rng)
+        return
+    for occ in args.occ or ["1,1,1", "2,2,2", "3,2,2", "3,2,3"]:
         form = occ.split(":", 1)[0] if occ.startswith("fused") else "split"
         A.set_bwd_form(form)
         occ = occ.split(":", 1)[1] if ":" in occ else ("3,2,3" if form != "split" else occ)

@@ -94,14 +94,22 @@ def train(model_name, batch_size, training_steps, stage, opts):
           f"betas={optimizer_state['betas']}; eps={optimizer_state['eps']}; "
           f"parameter count={sum([torch.numel(p) for p in optimizer_state['params']]):,}")
 
-    dataset = load_synthetic(cfg, batch_size * training_steps, seq_len=opts.seq_len, mlm=False, seed=0)
+    # --pad-fraction: that share of the rows is right-padded to a random length; --attention-mask:
+    # the rows' 0/1 mask goes to the model, whose attention then leaves the pad keys out (default
+    # off: pads attended to, as in the reference)
+    dataset = load_synthetic(cfg, batch_size * training_steps, seq_len=opts.seq_len, mlm=False, seed=0,
+                             pad_fraction=opts.pad_fraction, return_attention_mask=opts.attention_mask)
     sampler = DistributedSampler(dataset, num_replicas=world_size, rank=int(os.getenv("RANK", rank)))
-    loader = DeviceBatchLoader(dataset, batch_size=batch_size, sampler=sampler, device=device)
+    keys = ("input_ids", "labels") + (("attention_mask",) if opts.attention_mask else ())
+    loader = DeviceBatchLoader(dataset, batch_size=batch_size, sampler=sampler, device=device, keys=keys)
     model_engine.train()
     dist_log.comms_logger.reset()  # only the training loop's collectives are summed below
 
-    def train_step(input_ids, labels):
-        outputs = model_engine(input_ids, labels=labels)
+    def train_step(input_ids, labels, attention_mask=None):
+        if attention_mask is None:
+            outputs = model_engine(input_ids, labels=labels)
+        else:
+            outputs = model_engine(input_ids, labels=labels, attention_mask=attention_mask)
         model_engine.backward(outputs.loss)
         model_engine.step()
         return outputs.loss.detach()
@@ -133,9 +141,9 @@ def train(model_name, batch_size, training_steps, stage, opts):
     n = 0  # timed steps (graph warm-up steps trained before the clock started)
     for batch in batches:
         if graphed is not None and batch["input_ids"].shape == graphed.static["input_ids"].shape:
-            loss = graphed(input_ids=batch["input_ids"], labels=batch["labels"])
+            loss = graphed(**batch)   # (with --attention-mask: the mask is a third static input)
         else:
-            loss = train_step(batch["input_ids"], batch["labels"])
+            loss = train_step(**batch)
         n += 1
         if rank == 0:
             if not opts.no_memstats:
@@ -176,6 +184,10 @@ if __name__ == "__main__":
     parser.add_argument("--impl", default="auto", choices=["auto", "fused", "reference"])
     parser.add_argument("--num-gpus", type=int, default=None, help="spawn locally (like `deepspeed --num_gpus`)")
     parser.add_argument("--no-memstats", action="store_true")
+    parser.add_argument("--attention-mask", action="store_true",
+                        help="pass the rows' attention_mask to the model: pad keys are not attended to")
+    parser.add_argument("--pad-fraction", type=float, default=0.0,
+                        help="share of the synthetic rows right-padded to a random length")
     parser.add_argument("--graph", nargs="?", const="on", default="auto", choices=["auto", "on", "off"],
                         help="capture the whole training step in a hipGraph and replay it, at any ZeRO stage "
                              "(auto: on for one GPU, where batch-1 steps are host-launch bound)")
