@@ -342,6 +342,57 @@ __device__ __forceinline__ RowSrc row_src(const bf16* base, int ld, int nrows) {
   r.ld2 = ld * 2;
   return r;
 }
+// MFMA operand fragments of this lane's own row (query / key `row` of one (batch, head), chunks
+// 16 c + 8 hh): straight-line loads through a bounded resource, so a row past the end reads 0 with
+// no exec-masked branch -- a `valid ? load : 0` select puts each load in its own divergent region
+// with the consumer's s_waitcnt inside it, one serialized memory round trip per region.  The row
+// offset is per lane (voffset), which the bounds check covers.
+template <int D>
+__device__ __forceinline__ void load_frags(bf16x8 (&f)[D / 16], const bf16* base, int ld, int nrows, int row, int hh) {
+  const __amdgpu_buffer_rsrc_t rs = bounded_rsrc(base, nrows > 0 ? (uint32_t)(((nrows - 1) * ld + D) * 2) : 0u);
+  const int voff = (row * ld + 8 * hh) * 2;
+#pragma unroll
+  for (int c = 0; c < D / 16; ++c) f[c] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, voff + 32 * c, 0, 0));
+}
+// One fp32 per lane of a row statistic (lse, delta) through a bounded resource over its [S] row:
+// byte offset `off` past the end reads 0.
+__device__ __forceinline__ float load_stat(__amdgpu_buffer_rsrc_t rs, int off) {
+  return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0));
+}
+
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+// Epilogue store of a wave's 32 rows x D columns from NDB 32x32 accumulators (lane r = row, its
+// half-wave hh holds columns 8 k + 4 hh .. + 3 of column group k = 4 d + gq): bf16(acc * scale),
+// 16 bytes per lane per store.  One v_permlane32_swap per dword (vdst = group k, src = group
+// k + 1) moves the upper half's group-k columns down and the lower half's group-(k + 1) columns
+// up: the lower lanes then hold columns 8 k .. 8 k + 7 and the upper lanes 8 k + 8 .. 8 k + 15
+// (+16 bytes) -- half as many store instructions for the same bytes; the store tail is
+// issue-bound.  Both half-waves of a row share `valid`; `rowp` must be 16-byte aligned.
+template <int NDB>
+__device__ __forceinline__ void store_rows16(bf16* rowp, const f32x16 (&acc)[NDB], float scale, int hh, bool valid) {
+  u32x4 out[2 * NDB];
+#pragma unroll
+  for (int d = 0; d < NDB; ++d)
+#pragma unroll
+    for (int g2 = 0; g2 < 2; ++g2) {
+      bf16x4 a4, b4;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) { a4[t] = (bf16)(acc[d][8 * g2 + t] * scale); b4[t] = (bf16)(acc[d][8 * g2 + 4 + t] * scale); }
+      u32x2 a = __builtin_bit_cast(u32x2, a4), b = __builtin_bit_cast(u32x2, b4);
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const auto s = __builtin_amdgcn_permlane32_swap(a[t], b[t], false, false);
+        a[t] = s[0];
+        b[t] = s[1];
+      }
+      out[2 * d + g2] = u32x4{a[0], a[1], b[0], b[1]};
+    }
+  if (!valid) return;
+#pragma unroll
+  for (int i = 0; i < 2 * NDB; ++i) *reinterpret_cast<u32x4*>(rowp + 16 * i + 8 * hh) = out[i];
+}
+
 // One dropout keep word per lane (its query / key `pos`) per 32-wide word index: [W][S] uint32
 // words of one (batch, head); indices past W (and every index when there is no mask) read 0.
 struct WordSrc {
@@ -913,9 +964,9 @@ __global__ void __launch_bounds__(256, OCC) attn_bwd_dkdv_kernel(BwdArgs a) {
         bf16* dkp = a.dk + (size_t)(b * S + key) * a.ld + h * D;
         bf16* dvp = a.dv + (size_t)(b * S + key) * a.ld + h * D;
 #pragma unroll
-        for (int c = 0; c < D / 8; ++c) {   // both half-waves hold lane r's key: 4 of 8 columns each
-          *reinterpret_cast<bf16x4*>(dkp + 8 * c + 4 * hh) = bf16x4{};
-          *reinterpret_cast<bf16x4*>(dvp + 8 * c + 4 * hh) = bf16x4{};
+        for (int c = 0; c < D / 16; ++c) {   // both half-waves hold lane r's key: 8 of 16 columns each
+          *reinterpret_cast<bf16x8*>(dkp + 16 * c + 8 * hh) = bf16x8{};
+          *reinterpret_cast<bf16x8*>(dvp + 16 * c + 8 * hh) = bf16x8{};
         }
       }
       return;
@@ -934,18 +985,13 @@ __global__ void __launch_bounds__(256, OCC) attn_bwd_dkdv_kernel(BwdArgs a) {
   const __amdgpu_buffer_rsrc_t mrs = bounded_rsrc(drop ? (const void*)mrow : (const void*)a.lse, drop ? (uint32_t)Sp * 4u : 0u);
   const RowSrc qsrc = row_src<D>(a.q + (size_t)b * S * a.ld + h * D, a.ld, S);
   const RowSrc osrc = row_src<D>(a.dout + (size_t)b * S * a.ldo + h * D, a.ldo, S);
-  const float* lseb = a.lse + (size_t)bh * S;
-  const float* delb = a.delta + (size_t)bh * S;
+  // row statistics of one (batch, head): bounded resources over the [S] rows, so rows past S read 0
+  const __amdgpu_buffer_rsrc_t lse_rs = bounded_rsrc(a.lse + (size_t)bh * S, (uint32_t)S * 4u);
+  const __amdgpu_buffer_rsrc_t del_rs = bounded_rsrc(a.delta + (size_t)bh * S, (uint32_t)S * 4u);
 
   bf16x8 kf[NC], vf[NC];
-  {
-    const size_t off = (size_t)(b * S + (kvalid ? key : 0)) * a.ld + h * D;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      kf[c] = kvalid ? *reinterpret_cast<const bf16x8*>(a.k + off + 16 * c + 8 * hh) : bf16x8{};
-      vf[c] = kvalid ? *reinterpret_cast<const bf16x8*>(a.v + off + 16 * c + 8 * hh) : bf16x8{};
-    }
-  }
+  load_frags<D>(kf, a.k + (size_t)b * S * a.ld + h * D, a.ld, S, key, hh);   // keys past S: 0
+  load_frags<D>(vf, a.v + (size_t)b * S * a.ld + h * D, a.ld, S, key, hh);
   f32x16 dk[NDB], dv[NDB];
 #pragma unroll
   for (int d = 0; d < NDB; ++d) { dk[d] = f32x16{}; dv[d] = f32x16{}; }
@@ -953,16 +999,27 @@ __global__ void __launch_bounds__(256, OCC) attn_bwd_dkdv_kernel(BwdArgs a) {
   const int qstart = a.causal ? (kblk / BM) * BM : 0;
   const int nt = (S - qstart + BM - 1) / BM;
   TileLoader<D, BM> ql, ol;
+  // Raw lse / delta of a query tile, one row per thread of the first BM, issued straight behind the
+  // tile's Q / dO loads with no arithmetic on them: vmcnt retires in order, so a consumer placed
+  // here would drain the whole prefetch it was just issued behind (a full memory round trip at the
+  // head of every tile).  The values are transformed where they go to LDS (store_stats), after the
+  // tile's compute.  Threads past BM get an offset beyond any row: 0, without touching memory.
   float lse_r = 0.f, del_r = 0.f;
+  const int stat_off = threadIdx.x < BM ? (int)threadIdx.x * 4 : 0x40000000;
   auto load_stats = [&](int q0) {
+    lse_r = load_stat(lse_rs, q0 * 4 + stat_off);
+    del_r = load_stat(del_rs, q0 * 4 + stat_off);
+  };
+  auto store_stats = [&](int buf, int q0) {
     if (threadIdx.x < BM) {
-      const int qq = q0 + threadIdx.x;
-      lse_r = qq < S ? -lseb[qq] * kLog2e : 0.f;   // stored negated: P = 2^fma(s, sc2, -lse)
+      const bool in = q0 + (int)threadIdx.x < S;
+      float nl = in ? -lse_r * kLog2e : 0.f;       // stored negated: P = 2^fma(s, sc2, -lse)
       // a row without a key (lse = -inf): P = 2^(s - inf) = 0, not 2^(s + inf)
-      if constexpr (RANGE) lse_r = lse_r == INFINITY ? -INFINITY : lse_r;
+      if constexpr (RANGE) nl = nl == INFINITY ? -INFINITY : nl;
+      lse_s[buf][threadIdx.x] = nl;
       // dS = P (dP - delta); with dropout the kernel forms dS' = (1 - p) dS = Pm dP - P (1 - p) delta
       // (Pm = P * keep), so delta is stored pre-scaled and dK takes the 1 / (1 - p) at the end
-      del_r = qq < S ? -delb[qq] * (DROP ? 1.f - a.p : 1.f) : 0.f;
+      del_s[buf][threadIdx.x] = in ? -del_r * (DROP ? 1.f - a.p : 1.f) : 0.f;
     }
   };
   // L2 prefetch of the next query tile's keep words (BM words, value unused)
@@ -980,7 +1037,7 @@ __global__ void __launch_bounds__(256, OCC) attn_bwd_dkdv_kernel(BwdArgs a) {
   load_stats(qstart);
   ql.store_bwd(Qs[0], QP);
   ol.store_bwd(Os[0], QP);
-  if (threadIdx.x < BM) { lse_s[0][threadIdx.x] = lse_r; del_s[0][threadIdx.x] = del_r; }
+  store_stats(0, qstart);
   __syncthreads();
   for (int t = 0; t < nt; ++t) {
     const int buf = t & 1, q0 = qstart + t * BM;
@@ -1085,7 +1142,7 @@ __global__ void __launch_bounds__(256, OCC) attn_bwd_dkdv_kernel(BwdArgs a) {
     if (t + 1 < nt) {
       ql.store_bwd(Qs[buf ^ 1], QP);
       ol.store_bwd(Os[buf ^ 1], QP);
-      if (threadIdx.x < BM) { lse_s[buf ^ 1][threadIdx.x] = lse_r; del_s[buf ^ 1][threadIdx.x] = del_r; }
+      store_stats(buf ^ 1, q0 + BM);
     }
     __syncthreads();
   }
@@ -1105,19 +1162,8 @@ __global__ void __launch_bounds__(256, OCC) attn_bwd_dkdv_kernel(BwdArgs a) {
     row[a.H * D] = sk;
     row[2 * a.H * D] = sv;
   }
-  if (!kvalid) return;
-  bf16* dkp = a.dk + (size_t)(b * S + key) * a.ld + h * D;
-  bf16* dvp = a.dv + (size_t)(b * S + key) * a.ld + h * D;
-#pragma unroll
-  for (int d = 0; d < NDB; ++d)
-#pragma unroll
-    for (int gq = 0; gq < 4; ++gq) {
-      bf16x4 k4, v4;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) { k4[t] = (bf16)(dk[d][4 * gq + t] * dk_scale); v4[t] = (bf16)(dv[d][4 * gq + t] * dv_scale); }
-      *reinterpret_cast<bf16x4*>(dkp + d * 32 + 8 * gq + 4 * hh) = k4;
-      *reinterpret_cast<bf16x4*>(dvp + d * 32 + 8 * gq + 4 * hh) = v4;
-    }
+  store_rows16<NDB>(a.dk + (size_t)(b * S + key) * a.ld + h * D, dk, dk_scale, hh, kvalid);
+  store_rows16<NDB>(a.dv + (size_t)(b * S + key) * a.ld + h * D, dv, dv_scale, hh, kvalid);
 }
 
 // dQ: grid (ceil(S/128), B*H); block 256 = 4 waves x 32 queries (query on the lane, as in the
@@ -1153,36 +1199,6 @@ __global__ void __launch_bounds__(256, OCC) attn_bwd_dq_kernel(BwdArgs a) {
   const uint32_t* mrow = drop ? a.maskB + ((size_t)bh * a.W + min(q0 >> 5, a.W - 1)) * Sp : nullptr;
   const __amdgpu_buffer_rsrc_t mrs = bounded_rsrc(drop ? (const void*)mrow : (const void*)a.lse, drop ? (uint32_t)Sp * 4u : 0u);
 
-  bf16x8 qf[NC], of[NC];
-  {
-    const bf16* qp = a.q + ((size_t)(b * S + (qvalid ? q : 0)) * a.ld + h * D);
-    const bf16* op = a.dout + ((size_t)(b * S + (qvalid ? q : 0)) * a.ldo + h * D);
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      qf[c] = qvalid ? *reinterpret_cast<const bf16x8*>(qp + 16 * c + 8 * hh) : bf16x8{};
-      of[c] = qvalid ? *reinterpret_cast<const bf16x8*>(op + 16 * c + 8 * hh) : bf16x8{};
-    }
-  }
-  float lse2 = qvalid ? a.lse[(size_t)bh * S + q] * kLog2e : 0.f;
-  // a row without a key: every key it meets is masked below (P = 0 by select); +inf here also
-  // makes the unmasked exponent 2^(s - inf) = 0 instead of 2^(s + inf)
-  if constexpr (RANGE) lse2 = lse2 == -INFINITY ? INFINITY : lse2;
-  // delta = rowsum(dO * O) of this lane's query, from the dO fragments already in registers and
-  // one O row read (no separate delta pass re-reading dO); stored for the dK/dV kernel, which
-  // runs after this one
-  float dl;
-  {
-    const bf16* orow = a.o + ((size_t)(b * S + (qvalid ? q : 0)) * a.ldo + h * D);
-    float part = 0.f;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const bf16x8 ov = qvalid ? *reinterpret_cast<const bf16x8*>(orow + 16 * c + 8 * hh) : bf16x8{};
-#pragma unroll
-      for (int j = 0; j < 8; ++j) part = fmaf((float)ov[j], (float)of[c][j], part);
-    }
-    dl = xhalf_sum(part);
-    if (qvalid && hh == 0) a.delta[(size_t)bh * S + q] = dl;
-  }
   f32x16 dq[NDB];
 #pragma unroll
   for (int d = 0; d < NDB; ++d) dq[d] = f32x16{};
@@ -1206,14 +1222,44 @@ __global__ void __launch_bounds__(256, OCC) attn_bwd_dq_kernel(BwdArgs a) {
     asm volatile("" :: "v"(out));
     out = __builtin_amdgcn_raw_buffer_load_b32(mrs, lane * 4, k0 * 4, 0);
   };
-  kl0.load(ksrc, t0 * BN);
-  vl0.load(vsrc, t0 * BN);
-  kl0.store_bwd(Ks[0], KP);
-  vl0.store_bwd(Vs[0], KP);
+  // Prologue: one memory round trip.  Every load -- K/V tiles t0 and t0 + 1, then this lane's Q,
+  // dO and O fragments and its lse, all branch-free -- is issued before anything waits; tile t0
+  // goes to LDS as soon as it lands (it was issued first: a partial vmcnt) and delta is formed
+  // while the rest arrives.  With RING = 1 tile t0 has a register set of its own, which only
+  // lives here: the accumulators are not live yet, so the prologue stays below the loop's
+  // register peak.
+  bf16x8 qf[NC], of[NC];
+  float lse2, dl;
   {
+    TileLoader<D, BN> kpr, vpr;
+    TileLoader<D, BN>& kp = RING == 2 ? kl0 : kpr;
+    TileLoader<D, BN>& vp = RING == 2 ? vl0 : vpr;
     const int k1 = min(t0 + 1, last) * BN, k2 = min(t0 + 2, last) * BN;
+    kp.load(ksrc, t0 * BN);
+    vp.load(vsrc, t0 * BN);
     kl1.load(ksrc, k1); vl1.load(vsrc, k1); prefetch_words(k1, pf1);
+    bf16x8 ov[NC];
+    load_frags<D>(qf, a.q + (size_t)b * S * a.ld + h * D, a.ld, S, q, hh);       // rows past S: 0
+    load_frags<D>(of, a.dout + (size_t)b * S * a.ldo + h * D, a.ldo, S, q, hh);
+    load_frags<D>(ov, a.o + (size_t)b * S * a.ldo + h * D, a.ldo, S, q, hh);
+    lse2 = load_stat(bounded_rsrc(a.lse + (size_t)bh * S, (uint32_t)S * 4u), q * 4) * kLog2e;
+    // a row without a key: every key it meets is masked below (P = 0 by select); +inf here also
+    // makes the unmasked exponent 2^(s - inf) = 0 instead of 2^(s + inf)
+    if constexpr (RANGE) lse2 = lse2 == -INFINITY ? INFINITY : lse2;
+    asm volatile("" ::: "memory");   // keeps every load above issued ahead of the first wait
+    kp.store_bwd(Ks[0], KP);
+    vp.store_bwd(Vs[0], KP);
     if constexpr (RING == 2) { kl0.load(ksrc, k2); vl0.load(vsrc, k2); prefetch_words(k2, pf0); }
+    // delta = rowsum(dO * O) of this lane's query, from the dO fragments already in registers and
+    // one O row read (no separate delta pass re-reading dO); stored for the dK/dV kernel, which
+    // runs after this one
+    float part = 0.f;
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) part = fmaf((float)ov[c][j], (float)of[c][j], part);
+    dl = xhalf_sum(part);
+    if (qvalid && hh == 0) a.delta[(size_t)bh * S + q] = dl;
   }
   __syncthreads();
   auto tile = [&](auto set_c, int t) {
@@ -1320,17 +1366,7 @@ __global__ void __launch_bounds__(256, OCC) attn_bwd_dq_kernel(BwdArgs a) {
     const float sq = colsum32(vq, r);
     a.bias_part[((size_t)b * gridDim.x * 4 + (qblk >> 5) + w) * (3 * a.H * D) + h * D + colsum_col(r, hh)] = sq;
   }
-  if (!qvalid) return;
-  bf16* qp = a.dq + (size_t)(b * S + q) * a.ld + h * D;
-#pragma unroll
-  for (int d = 0; d < NDB; ++d)
-#pragma unroll
-    for (int gq = 0; gq < 4; ++gq) {
-      bf16x4 v4;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) v4[t] = (bf16)(dq[d][4 * gq + t] * a.scale);
-      *reinterpret_cast<bf16x4*>(qp + d * 32 + 8 * gq + 4 * hh) = v4;
-    }
+  store_rows16<NDB>(a.dq + (size_t)(b * S + q) * a.ld + h * D, dq, a.scale, hh, qvalid);
 }
 
 #if DTD_ATTN_FUSED_BWD   // experimental builds only (DTD_BUILD_EXPERIMENTAL=1, ops/build.py): the
