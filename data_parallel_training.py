@@ -81,11 +81,15 @@ def train(rank, world_size, batch_size, training_steps, bucket_size, model_name,
 
     # --pad-fraction: that share of the rows is right-padded to a random length; --attention-mask:
     # the rows' 0/1 mask goes to the model, whose attention then leaves the pad keys out (and the
-    # kernels skip their tiles) -- default off: pads attended to, as in the reference
+    # kernels skip their tiles) -- default off: pads attended to, as in the reference.
+    # --pack-docs N: every row holds 1 to N documents (and, with --pad-fraction, a padded tail); the
+    # rows' segment_ids go to the model: attention stays inside a document, positions restart
     dataset = load_synthetic(cfg, batch_size * training_steps, seq_len=opts.seq_len, seed=0,
-                             pad_fraction=opts.pad_fraction, return_attention_mask=opts.attention_mask)
+                             pad_fraction=opts.pad_fraction, return_attention_mask=opts.attention_mask,
+                             max_docs=opts.pack_docs)
     sampler = DistributedSampler(dataset, num_replicas=world_size, rank=rank)
-    keys = ("input_ids", "labels") + (("attention_mask",) if opts.attention_mask else ())
+    keys = ("input_ids", "labels") + (("attention_mask",) if opts.attention_mask else ()) \
+        + (("segment_ids",) if opts.pack_docs else ())
     loader = DeviceBatchLoader(dataset, batch_size=batch_size, sampler=sampler, device=device, keys=keys)
 
     progress = None
@@ -97,9 +101,11 @@ def train(rank, world_size, batch_size, training_steps, bucket_size, model_name,
             pass
     if opts.markers:
         enable_markers()
-    def step(input_ids, labels, attention_mask=None):
+    def step(input_ids, labels, attention_mask=None, segment_ids=None):
         with marker("forward"):
-            if attention_mask is None:
+            if segment_ids is not None:
+                out = ddp(input_ids, labels=labels, segment_ids=segment_ids)
+            elif attention_mask is None:
                 out = ddp(input_ids, labels=labels)
             else:
                 out = ddp(input_ids, labels=labels, attention_mask=attention_mask)
@@ -138,7 +144,8 @@ def train(rank, world_size, batch_size, training_steps, bucket_size, model_name,
     n = 0  # timed steps (graph warm-up steps trained before the clock started)
     for batch in batches:
         timer.start()
-        # (with --attention-mask the mask is the batch's third entry: a third static graph input)
+        # (with --attention-mask / --pack-docs the mask / segment ids are the batch's third entry: a
+        # third static graph input)
         if graphed is not None and batch["input_ids"].shape == graphed.static["input_ids"].shape:
             loss = graphed(**batch)
         else:
@@ -157,7 +164,10 @@ def train(rank, world_size, batch_size, training_steps, bucket_size, model_name,
     print(f"\nTotal Training Time: {elapsed:.2f} seconds")
     if rank == 0:
         tokens = n * batch_size * opts.seq_len * world_size
-        print(json.dumps({"tokens_per_s": round(tokens / max(elapsed, 1e-9), 1), "steps_per_rank": n + len(warm), "timed_steps": n,
+        # trained tokens: the share of the dataset's positions that carry a label
+        labelled = float((dataset.labels != -100).float().mean())
+        print(json.dumps({"tokens_per_s": round(tokens / max(elapsed, 1e-9), 1),
+                          "labelled_tokens_per_s": round(labelled * tokens / max(elapsed, 1e-9), 1), "steps_per_rank": n + len(warm), "timed_steps": n,
                           "world_size": world_size, "final_loss": round(float(loss.detach()), 4) if loss is not None else None}))
         if opts.metrics_json:
             timer.write(opts.metrics_json, {"model": name, "per_gpu_batch": batch_size, "seq_len": opts.seq_len,
@@ -190,10 +200,15 @@ if __name__ == "__main__":
                         help="pass the rows' attention_mask to the model: pad keys are not attended to")
     parser.add_argument("--pad-fraction", type=float, default=0.0,
                         help="share of the synthetic rows right-padded to a random length")
+    parser.add_argument("--pack-docs", type=int, default=0, metavar="N",
+                        help="sequence packing: cut every synthetic row into 1 to N documents and pass the rows' "
+                             "segment_ids to the model (excludes --attention-mask)")
     parser.add_argument("--graph", nargs="?", const="on", default="auto", choices=["auto", "on", "off"],
                         help="capture the whole training step (bucket all-reduces included) in a hipGraph and "
                              "replay it (auto: on at <= 32 sequences per GPU, where the step is host-launch bound)")
     args = parser.parse_args()
+    if args.pack_docs and args.attention_mask:
+        parser.error("--pack-docs and --attention-mask are mutually exclusive (segment id 0 marks the padding)")
 
     device_count = args.device_count or get_device_count()
     launch(train, args=(args.batch_size, args.training_steps, args.bucket_size, args.model, args),

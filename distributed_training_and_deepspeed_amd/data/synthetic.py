@@ -9,7 +9,9 @@ shape, framing ([CLS] ... [SEP] for BERT) and the same masking law, generated
 deterministically from a seed.  ``pad_fraction`` optionally right-pads rows with the pad id
 to mimic short wikitext lines; ``return_attention_mask=True`` adds the matching 0/1
 ``attention_mask`` column (ones over each row's drawn length), which the models turn into key
-ranges so the pads are not attended to.
+ranges so the pads are not attended to.  ``max_docs > 0`` packs rows instead: each row is cut into
+1 to ``max_docs`` documents of random lengths (each framed [CLS] ... [SEP] for BERT) and a
+``segment_ids`` column (0 = padding, 1, 2, ... per document) is added -- data/packing.py.
 """
 from __future__ import annotations
 
@@ -17,6 +19,7 @@ import torch
 from torch.utils.data import Dataset
 
 from ..models.config import TransformerConfig
+from .packing import packed_causal_labels
 
 IGNORE_INDEX = -100
 
@@ -72,23 +75,60 @@ def synthetic_token_rows_lengths(n: int, seq_len: int, cfg: TransformerConfig, g
     return ids, special, row_len
 
 
+def cut_into_documents(ids: torch.Tensor, row_len: torch.Tensor, cfg: TransformerConfig, max_docs: int,
+                       generator: torch.Generator) -> torch.Tensor:
+    """Cut the first ``row_len[i]`` tokens of every row into 1 to ``max_docs`` documents of random
+    lengths (at least 2 tokens each) and frame each as [CLS] ... [SEP] for BERT, in place.  Returns
+    the ``segment_ids`` ([n, seq_len] int64: 1, 2, ... per document, 0 over the padded tail)."""
+    n, S = ids.shape
+    seg = torch.zeros((n, S), dtype=torch.int64)
+    want = torch.randint(1, max_docs + 1, (n,), generator=generator)
+    for i in range(n):
+        L = int(row_len[i])
+        # distinct random cut points, kept when they leave 2 tokens on either side
+        cand = (torch.randperm(max(L - 3, 0), generator=generator)[: int(want[i]) - 1] + 2).sort().values.tolist()
+        cuts = [0]
+        for c in cand:
+            if c - cuts[-1] >= 2 and L - c >= 2:
+                cuts.append(c)
+        cuts.append(L)
+        for d, (lo, hi) in enumerate(zip(cuts[:-1], cuts[1:])):
+            seg[i, lo:hi] = d + 1
+            if cfg.family == "bert":
+                ids[i, lo] = 101
+                ids[i, hi - 1] = 102
+    return seg
+
+
 class SyntheticLMDataset(Dataset):
     """Map-style dataset of {'input_ids', 'labels'} rows, statically masked like util.py.
     ``return_attention_mask=True`` adds an 'attention_mask' column: a prefix of ones of each row's
     drawn length (not ``ids != pad``: a random token can equal the pad id)."""
 
     attention_mask = None   # [n, seq_len] int64 0/1 when requested
+    segment_ids = None      # [n, seq_len] int64 document ids of packed rows (max_docs > 0)
 
     def __init__(self, cfg: TransformerConfig, num_samples: int, seq_len: int = 512, mlm: bool | None = None,
-                 seed: int = 0, pad_fraction: float = 0.0, return_attention_mask: bool = False):
+                 seed: int = 0, pad_fraction: float = 0.0, return_attention_mask: bool = False, max_docs: int = 0):
+        """``max_docs > 0``: packed rows (module docstring) with a 'segment_ids' column.  Causal
+        labels are then -100 on every document's first token and on pads, so that after the head's
+        shift no position predicts across a boundary; MLM labels follow the unchanged masking law,
+        every document's [CLS] / [SEP] exempt.  ``max_docs = 0`` draws exactly the rows it always did."""
         self.cfg = cfg
         self.mlm = (cfg.family == "bert") if mlm is None else mlm
         g = torch.Generator().manual_seed(seed)
         ids, special, row_len = synthetic_token_rows_lengths(num_samples, seq_len, cfg, g, pad_fraction)
         if return_attention_mask:
             self.attention_mask = (torch.arange(seq_len).view(1, -1) < row_len.view(-1, 1)).to(torch.int64)
+        if max_docs > 0:
+            self.segment_ids = cut_into_documents(ids, row_len, cfg, max_docs, g)
+            special = torch.zeros_like(ids, dtype=torch.bool)
+            for s in set(cfg.special_token_ids):
+                special |= ids == s
         if self.mlm:
             self.input_ids, self.labels = mlm_mask_tokens(ids, special, cfg.vocab_size, cfg.mask_token_id, g)
+        elif max_docs > 0:
+            self.input_ids, self.labels = ids, packed_causal_labels(ids, self.segment_ids)
         else:
             self.input_ids, self.labels = ids, ids.clone()  # util.py:54-58: pads included
 
@@ -99,6 +139,8 @@ class SyntheticLMDataset(Dataset):
         row = {"input_ids": self.input_ids[i], "labels": self.labels[i]}
         if self.attention_mask is not None:
             row["attention_mask"] = self.attention_mask[i]
+        if self.segment_ids is not None:
+            row["segment_ids"] = self.segment_ids[i]
         return row
 
     def select(self, indices) -> "SyntheticLMDataset":
@@ -108,14 +150,16 @@ class SyntheticLMDataset(Dataset):
         out.cfg, out.mlm = self.cfg, self.mlm
         out.input_ids, out.labels = self.input_ids[idx], self.labels[idx]
         out.attention_mask = None if self.attention_mask is None else self.attention_mask[idx]
+        out.segment_ids = None if self.segment_ids is None else self.segment_ids[idx]
         return out
 
 
 def load_synthetic(cfg: TransformerConfig, num_samples: int, seq_len: int = 512, mlm: bool | None = None,
-                   seed: int = 0, pad_fraction: float = 0.0, return_attention_mask: bool = False) -> SyntheticLMDataset:
+                   seed: int = 0, pad_fraction: float = 0.0, return_attention_mask: bool = False,
+                   max_docs: int = 0) -> SyntheticLMDataset:
     """Stand-in for ``util.load_wikitext`` (same columns, same masking law)."""
     return SyntheticLMDataset(cfg, num_samples, seq_len, mlm=mlm, seed=seed, pad_fraction=pad_fraction,
-                              return_attention_mask=return_attention_mask)
+                              return_attention_mask=return_attention_mask, max_docs=max_docs)
 
 
 class NativeSyntheticLM:

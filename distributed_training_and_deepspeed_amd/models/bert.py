@@ -9,7 +9,10 @@ cross entropy with ignore_index -100 over all labelled positions.  By default no
 is applied (the reference never passes one, so pads are attended to); ``forward(...,
 attention_mask=...)`` takes HF's 0/1 ``[B, S]`` key-padding mask of a left- or right-padded batch
 (contiguous masks only, ``ops.attention.key_range_from_mask``).  Position ids stay ``arange(S)``,
-which equals HF's for right-padded batches.  There is no pooler (add_pooling_layer=False).
+which equals HF's for right-padded batches.  ``forward(..., segment_ids=...)`` takes a packed
+batch instead (integer ``[B, S]``, 0 = padding, one non-zero id per contiguous document,
+``ops.attention.doc_range_from_segment_ids``): attention stays inside each document and the learned
+positions restart at each one; it excludes ``attention_mask``.  There is no pooler (add_pooling_layer=False).
 Parameter count for bert-base-cased: 108,340,804.
 """
 from __future__ import annotations
@@ -21,7 +24,7 @@ from torch import nn
 
 from .config import BERT_BASE, TransformerConfig, get_config
 from .layers import Embeddings, MLMHead
-from ..ops.attention import key_range_from_mask
+from ..ops.attention import doc_position_ids, doc_range_from_segment_ids, key_range_from_mask
 from .transformer import Runtime, TransformerLayer, prefetch_masks, stage_dgrad_transposes
 
 
@@ -52,20 +55,33 @@ class BertForMaskedLM(nn.Module):
         """Parameters shared between units (tied decoder / word embeddings)."""
         return [self.embeddings.word] if self.head.decoder_w is None else []
 
-    def encode(self, input_ids: torch.Tensor, attention_mask: torch.Tensor | None = None) -> torch.Tensor:
+    def encode(self, input_ids: torch.Tensor, attention_mask: torch.Tensor | None = None,
+               segment_ids: torch.Tensor | None = None) -> torch.Tensor:
+        if attention_mask is not None and segment_ids is not None:
+            raise ValueError("attention_mask and segment_ids are mutually exclusive (segment id 0 marks padding)")
         if input_ids.is_cuda and self.training:
             prefetch_masks(self.layers, input_ids)
         # one conversion per forward (on the device, no host sync); every layer gets the ranges
         key_range = key_range_from_mask(attention_mask) if attention_mask is not None else None
-        x = self.embeddings(input_ids)
+        doc_range = position_ids = None
+        if segment_ids is not None:
+            if segment_ids.shape != input_ids.shape:
+                raise ValueError(f"segment_ids must be {tuple(input_ids.shape)}, got {tuple(segment_ids.shape)}")
+            doc_range = doc_range_from_segment_ids(segment_ids)
+            position_ids = doc_position_ids(doc_range)      # restart at every document; pads take 0
+        x = self.embeddings(input_ids) if position_ids is None else self.embeddings(input_ids, position_ids=position_ids)
         for layer in self.layers:
-            x = layer(x) if key_range is None else layer(x, key_range=key_range)
+            if doc_range is not None:
+                x = layer(x, doc_range=doc_range)
+            else:
+                x = layer(x) if key_range is None else layer(x, key_range=key_range)
         stage_dgrad_transposes(self.layers, x)
         return x
 
     def forward(self, input_ids: torch.Tensor, labels: torch.Tensor | None = None,
-                return_logits: bool = False, attention_mask: torch.Tensor | None = None) -> MaskedLMOutput:
-        x = self.encode(input_ids, attention_mask)
+                return_logits: bool = False, attention_mask: torch.Tensor | None = None,
+                segment_ids: torch.Tensor | None = None) -> MaskedLMOutput:
+        x = self.encode(input_ids, attention_mask, segment_ids)
         out = MaskedLMOutput()
         if labels is not None:
             out.loss = self.head(x, labels)

@@ -15,6 +15,14 @@ or right-padded, ``ops.attention.key_range_from_mask``); without it pads are att
 reference.  Position ids stay ``arange(S)``: equal to HF's for right-padded batches, and for BLOOM
 (ALiBi, no position table) under either padding side.  For a LEFT-padded OPT or GPT-2 batch HF
 derives the positions from the mask (first real token = position 0); here they are not shifted.
+
+``forward(..., segment_ids=...)`` takes a packed batch instead (integer ``[B, S]``, 0 = padding, one
+non-zero id per contiguous document, ``ops.attention.doc_range_from_segment_ids``): attention is
+causal inside each document, the learned positions of OPT / GPT-2 restart at each document (BLOOM's
+ALiBi keeps absolute key positions: a per-row constant the softmax cancels), and it excludes
+``attention_mask``.  The loss does not cross a boundary when the labels of every document's first
+token are -100 (data/synthetic.py, data/text.py write them so): the head's shift then leaves no
+position predicting the next document.
 """
 from __future__ import annotations
 
@@ -25,7 +33,7 @@ from torch import nn
 
 from .config import BLOOM_560M, TransformerConfig, get_config
 from .layers import Embeddings, LayerNorm, LMHead
-from ..ops.attention import key_range_from_mask
+from ..ops.attention import doc_position_ids, doc_range_from_segment_ids, key_range_from_mask
 from .transformer import Runtime, TransformerLayer, prefetch_masks, stage_dgrad_transposes
 
 
@@ -57,22 +65,35 @@ class CausalLM(nn.Module):
         """Parameters shared between units (LM head tied to the word embeddings)."""
         return [self.embeddings.word]
 
-    def encode(self, input_ids: torch.Tensor, attention_mask: torch.Tensor | None = None) -> torch.Tensor:
+    def encode(self, input_ids: torch.Tensor, attention_mask: torch.Tensor | None = None,
+               segment_ids: torch.Tensor | None = None) -> torch.Tensor:
+        if attention_mask is not None and segment_ids is not None:
+            raise ValueError("attention_mask and segment_ids are mutually exclusive (segment id 0 marks padding)")
         if input_ids.is_cuda and self.training:
             prefetch_masks(self.layers, input_ids)
         # one conversion per forward (on the device, no host sync); every layer gets the ranges
         key_range = key_range_from_mask(attention_mask) if attention_mask is not None else None
-        x = self.embeddings(input_ids)
+        doc_range = position_ids = None
+        if segment_ids is not None:
+            if segment_ids.shape != input_ids.shape:
+                raise ValueError(f"segment_ids must be {tuple(input_ids.shape)}, got {tuple(segment_ids.shape)}")
+            doc_range = doc_range_from_segment_ids(segment_ids)
+            position_ids = doc_position_ids(doc_range)      # restart at every document; pads take 0
+        x = self.embeddings(input_ids) if position_ids is None else self.embeddings(input_ids, position_ids=position_ids)
         for layer in self.layers:
-            x = layer(x) if key_range is None else layer(x, key_range=key_range)
+            if doc_range is not None:
+                x = layer(x, doc_range=doc_range)
+            else:
+                x = layer(x) if key_range is None else layer(x, key_range=key_range)
         stage_dgrad_transposes(self.layers, x)
         if self.final_ln is not None:
             x = self.final_ln(x)
         return x
 
     def forward(self, input_ids: torch.Tensor, labels: torch.Tensor | None = None,
-                return_logits: bool = False, attention_mask: torch.Tensor | None = None) -> CausalLMOutput:
-        x = self.encode(input_ids, attention_mask)
+                return_logits: bool = False, attention_mask: torch.Tensor | None = None,
+                segment_ids: torch.Tensor | None = None) -> CausalLMOutput:
+        x = self.encode(input_ids, attention_mask, segment_ids)
         out = CausalLMOutput()
         if labels is not None:
             out.loss = self.head(x, labels)

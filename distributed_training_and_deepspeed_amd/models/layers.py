@@ -85,7 +85,7 @@ _FUSED_EMBED_LN = [os.environ.get("DTD_FUSED_EMBED_LN", "1") == "1"]
 
 class _EmbedFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, ids, mod, *params):
+    def forward(ctx, ids, mod, position_ids, *params):
         c, rt = mod.cfg, mod.rt
         B, S = ids.shape
         h = c.hidden_size
@@ -96,13 +96,14 @@ class _EmbedFn(torch.autograd.Function):
         sid = rt.rng.sid(mod.sid)
         fused = None
         if mod.ln_g is not None and _FUSED_EMBED_LN[0]:
-            # gather-sum + LN + dropout in one pass (bit-identical to the three passes below)
+            # gather-sum + LN + dropout in one pass (bit-identical to the three passes below);
+            # None with position ids, which the one-pass kernel does not read
             fused = Fx.embed_ln_fwd(ids, word, pos, typ, S, c.position_offset, mod.ln_g, mod.ln_b, c.ln_eps,
-                                    p, rt.rng, sid)
+                                    p, rt.rng, sid, position_ids=position_ids)
         if fused is not None:
             out, z, m, r = fused
         else:
-            z = Fx.embed_fwd(ids, word, pos, typ, S, c.position_offset)
+            z = Fx.embed_fwd(ids, word, pos, typ, S, c.position_offset, position_ids=position_ids)
             if mod.ln_g is not None:
                 _, x, m, r = Fx.ln_fwd(None, z, mod.ln_g, mod.ln_b, c.ln_eps, 0.0, rt.rng, 0)
             else:
@@ -110,6 +111,7 @@ class _EmbedFn(torch.autograd.Function):
             out = Fx.dropout(x, p, rt.rng, sid)
         ctx.save_for_backward(ids, z, m, r)
         ctx.mod, ctx.p, ctx.sid, ctx.rng = mod, p, sid, rt.rng
+        ctx.position_ids = position_ids
         return out.view(B, S, h)
 
     @staticmethod
@@ -132,7 +134,7 @@ class _EmbedFn(torch.autograd.Function):
         grad_done(mod.word)
         if mod.pos is not None:
             dst, acc = grad_dst(mod.pos)
-            Fx.embed_pos_bwd(dz, dst, B, S, c.position_offset, acc)
+            Fx.embed_pos_bwd(dz, dst, B, S, c.position_offset, acc, position_ids=ctx.position_ids)
             grad_done(mod.pos)
         if mod.tok_type is not None:
             dst, acc = grad_dst(mod.tok_type)
@@ -140,7 +142,7 @@ class _EmbedFn(torch.autograd.Function):
                 dst.zero_()
             Fx.bias_grad(dz, dst[0], True)
             grad_done(mod.tok_type)
-        return (None, None) + (None,) * len(mod.params())
+        return (None, None, None) + (None,) * len(mod.params())
 
 
 class Embeddings(nn.Module):
@@ -170,15 +172,21 @@ class Embeddings(nn.Module):
     def params(self):
         return tuple(p for p in (self.word, self.pos, self.tok_type, self.ln_g, self.ln_b) if p is not None)
 
-    def forward(self, ids: torch.Tensor) -> torch.Tensor:
+    def forward(self, ids: torch.Tensor, position_ids: torch.Tensor | None = None) -> torch.Tensor:
+        """``position_ids``: optional integer [B, S] positions of a packed batch (they restart at
+        every document; ``position_offset`` is added here).  Ignored without a position table (BLOOM)."""
+        if self.pos is None:
+            position_ids = None
         self._dtd_weightless_bwd = self.rt.use_fused(self.word)   # see TransformerLayer.forward
         if self._dtd_weightless_bwd:
             note_use(self.params())
-            return _EmbedFn.apply(ids, self, *self.params())
+            return _EmbedFn.apply(ids, self, position_ids, *self.params())
         c = self.cfg
         B, S = ids.shape
         x = F.embedding(ids, self.word, padding_idx=c.pad_token_id if c.family in ("bert", "opt") else None)
-        if self.pos is not None:
+        if self.pos is not None and position_ids is not None:
+            x = x + F.embedding(position_ids.to(torch.int64) + c.position_offset, self.pos)
+        elif self.pos is not None:
             x = x + self.pos[c.position_offset:c.position_offset + S][None]
         if self.tok_type is not None:
             x = x + self.tok_type[0][None, None]

@@ -182,20 +182,24 @@ class TransformerLayer(nn.Module):
         if pend is not None:
             self._prefetched = (sid, B, S, pend)
 
-    def forward(self, x: torch.Tensor, key_range: torch.Tensor | None = None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, key_range: torch.Tensor | None = None, doc_range=None) -> torch.Tensor:
         """x: [B, S, h] -> [B, S, h].  ``key_range``: optional int32 [B, 2] per-sequence key
         ranges (the key-padding mask, ops/attention.py): keys outside [lo, hi) are not attended
-        to; padded query rows are still computed."""
+        to; padded query rows are still computed.  ``doc_range``: optional document spans of a
+        packed batch (``ops.attention.DocRange``): attention stays inside each document; exclusive
+        with ``key_range``."""
+        if key_range is not None and doc_range is not None:
+            raise ValueError("key_range and doc_range are mutually exclusive")
         # the fused backward reads the parameters at backward time (no saved weight views): ZeRO-3
         # may release and later re-gather them in between (parallel/zero.py)
         self._dtd_weightless_bwd = self.rt.use_fused(x)
         if self._dtd_weightless_bwd:
             note_use(self.params())
-            return _FusedLayerFn.apply(x, self, key_range, *self.params())
-        return self._reference(x, key_range)
+            return _FusedLayerFn.apply(x, self, key_range, doc_range, *self.params())
+        return self._reference(x, key_range, doc_range)
 
     # ------------------------------------------------------------------ reference path
-    def _reference(self, x: torch.Tensor, key_range: torch.Tensor | None = None) -> torch.Tensor:
+    def _reference(self, x: torch.Tensor, key_range: torch.Tensor | None = None, doc_range=None) -> torch.Tensor:
         c, rt = self.cfg, self.rt
         B, S, h = x.shape
         H, D = c.num_heads, c.head_dim
@@ -211,8 +215,10 @@ class TransformerLayer(nn.Module):
                 s = s + self.alibi.view(1, H, 1, 1).to(s.dtype) * torch.arange(S, device=s.device, dtype=s.dtype)
             if c.causal:
                 s = s.masked_fill(torch.ones(S, S, dtype=torch.bool, device=s.device).triu(1), float("-inf"))
-            if key_range is not None:
-                s = s.masked_fill(A._range_mask(key_range, B, S, s.device), float("-inf"))
+            if key_range is not None or doc_range is not None:
+                outside = A._range_mask(key_range, B, S, s.device) if key_range is not None \
+                    else A._doc_mask(doc_range, B, S, s.device)
+                s = s.masked_fill(outside, float("-inf"))
                 # a row without a key (all -inf, softmax NaN) attends to nothing: probabilities 0
                 dead = (s == float("-inf")).all(-1, keepdim=True)
                 prob = torch.softmax(s.float().masked_fill(dead, 0.0), -1).masked_fill(dead, 0.0).to(s.dtype)
@@ -305,7 +311,7 @@ def _proj_ln(inp, w, bias, res, gamma, beta, eps, p, rng, sid, store_z):
 
 class _FusedLayerFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, layer: TransformerLayer, key_range, *params):
+    def forward(ctx, x, layer: TransformerLayer, key_range, doc_range, *params):
         c, rt = layer.cfg, layer.rt
         (qkv_w, qkv_b, o_w, o_b, g1, b1, w1, bf1, w2, bf2, g2, b2) = params
         B, S, h = x.shape
@@ -332,7 +338,7 @@ class _FusedLayerFn(torch.autograd.Function):
             a_in = x2d
         qkv = G.linear_any(a_in, qkv_w, qkv_b)
         actx, lse, amask = A.attn_fwd(qkv, B, S, H, D, c.causal, layer.alibi, p_a, rng, sa, masks=pend,
-                                      key_range=key_range)
+                                      key_range=key_range, doc_range=doc_range)
         ln_fo = (_LN_MEMEFF[0] if rt.ln_memeff is None else rt.ln_memeff) and not c.pre_ln
         if c.pre_ln:
             o = G.linear_any(actx, o_w, o_b)
@@ -367,6 +373,7 @@ class _FusedLayerFn(torch.autograd.Function):
         ctx.layer = layer
         ctx.amask = amask  # attention dropout keep bits (kernel path) for the backward
         ctx.key_range = key_range  # the attention's key ranges (integer, no gradient), same in the backward
+        ctx.doc_range = doc_range  # likewise the document spans of a packed batch
         ctx.rng = rng  # the RngState of this forward's device (pipeline stages differ)
         ctx.meta = (B, S, h, H, D, p_h, p_a, sa, s1, s2)
         ctx.ffn_g = ffn_g
@@ -447,10 +454,10 @@ class _FusedLayerFn(torch.autograd.Function):
         # the qkv bias gradient comes out of the attention-backward epilogues (column partials)
         if _FUSED_QKV_BIAS[0]:
             dqkv = A.attn_bwd(dctx, qkv, actx, lse, B, S, H, D, c.causal, layer.alibi, p_a, rng, sa, ctx.amask,
-                              dbias=_pair(qkv_b), key_range=ctx.key_range)
+                              dbias=_pair(qkv_b), key_range=ctx.key_range, doc_range=ctx.doc_range)
         else:
             dqkv = A.attn_bwd(dctx, qkv, actx, lse, B, S, H, D, c.causal, layer.alibi, p_a, rng, sa, ctx.amask,
-                              key_range=ctx.key_range)
+                              key_range=ctx.key_range, doc_range=ctx.doc_range)
             Fx.bias_grad(dqkv, *_pair(qkv_b))
         grad_done(qkv_b)
         if c.pre_ln:
@@ -464,7 +471,7 @@ class _FusedLayerFn(torch.autograd.Function):
             emit_wgrad(qkv_w, dqkv, x2d, async_ok=True)
             # in place: dz1 is this backward's own buffer (no C copy); NT form through the transposed weight
             dx = G.dgrad_add_(dz1, dqkv, qkv_w)
-        return (dx.view(B, S, h), None, None) + (None,) * 12
+        return (dx.view(B, S, h), None, None, None) + (None,) * 12
 
 
 def _pair(p):

@@ -52,6 +52,7 @@ _SIGS = {
     "dtd_xent_grad_scale": (I, [P, SZ, P, P]),
     # embed.hip
     "dtd_embed_fwd": (I, [I, P, P, P, P, P, P, I, I, I, I, P]),
+    "dtd_embed_fwd_pos": (I, [I, P, P, P, P, P, P, P, I, I, I, I, P]),
     "dtd_embed_word_bwd": (I, [I, I, P, P, P, P, I, I, I, I, P]),
     "dtd_embed_pos_bwd": (I, [I, I, P, P, I, I, I, I, I, P]),
     "dtd_scatter_rows": (I, [P, P, P, I, P, I, I, P]),
@@ -68,6 +69,10 @@ _SIGS = {
     # (the _range forms: the same arguments, then the int32 [B][2] key ranges before the stream)
     "dtd_attn_fwd_range": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, F, P, U32, P, P]),
     "dtd_attn_bwd_range": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, F, P, P, P]),
+    # (the _doc forms, sequence packing: the same arguments, then one int32 array -- the [B][S][2]
+    # document spans followed by the [B][ceil(S/128)][2] block bounds -- before the stream)
+    "dtd_attn_fwd_doc": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, F, P, U32, P, P]),
+    "dtd_attn_bwd_doc": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, F, P, P, P]),
     "dtd_attn_masks": (I, [P, I, I, I, F, P, U32, P]),
     "dtd_attn_set_bwd_form": (I, [I]),
     "dtd_attn_set_bwd_kernels": (I, [I]),

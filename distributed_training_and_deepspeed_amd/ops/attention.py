@@ -14,6 +14,14 @@ attend to the valid keys, as in HF models).  A row left without a key -- lo >= h
 q < lo -- has ctx = 0, lse = -inf and contributes nothing to any gradient.  Dropout keep bits stay
 indexed by the absolute (b, h, q, key), so a range does not change which bits a pair draws.
 
+Sequence packing: ``doc_range`` (``DocRange``, from ``doc_range_from_segment_ids``) gives every
+position the half-open span (lo, hi) of its document, int32 ``[B, S, 2]``, (0, 0) for a pad.  Query i
+attends key j iff lo_i <= j < hi_i (and j <= i when causal) -- block-diagonal attention over the
+documents of a row; the relation is symmetric.  Everything else is as for a key range (which it
+excludes: padding is an empty span here): the mask comes before ALiBi, whose bias stays slope *
+absolute key position, the keep bits stay absolutely indexed, and a row without a key -- a pad -- has
+ctx = 0, lse = -inf, dq = 0 and contributes to no gradient; pad keys get dk = dv = 0.
+
 Reference semantics: HF BertSelfAttention eager path (matmul, softmax, dropout, matmul --
 SURVEY.md K2, reference model/transformer.py:80-86); the reference never passes an
 attention mask for BERT (data_parallel_training.py:53), so by default (no ``key_range``) padding
@@ -23,6 +31,7 @@ from __future__ import annotations
 
 import math
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -77,6 +86,100 @@ def key_range_from_mask(attention_mask: torch.Tensor, check: bool = False) -> to
     return torch.stack([lo, hi], 1).contiguous()
 
 
+class DocRange(NamedTuple):
+    """Document spans of a packed batch.  ``ranges``: int32 [B, S, 2], (lo, hi) of each position's
+    document, (0, 0) for a pad.  ``blocks``: int32 [B, ceil(S / 128), 2], (min lo, max hi) over each
+    128-position block's non-empty rows, (0, 0) for a block without one -- the tile range of the
+    workgroup that owns the block.  Both are views of ``flat``, the kernels' one argument."""
+    ranges: torch.Tensor
+    blocks: torch.Tensor
+    flat: torch.Tensor
+
+
+_DOC_BLOCK = 128     # positions per workgroup of the attention kernels
+
+
+def _doc_pack(ranges: torch.Tensor) -> DocRange:
+    """DocRange of int [B, S, 2] spans: the block bounds are derived on the device, no sync."""
+    B, S = ranges.shape[:2]
+    nb = (S + _DOC_BLOCK - 1) // _DOC_BLOCK
+    r = ranges.to(torch.int32)
+    lo, hi = r[..., 0], r[..., 1]
+    live = hi > lo
+    pad = nb * _DOC_BLOCK - S
+    blo = torch.nn.functional.pad(torch.where(live, lo, torch.full_like(lo, S)), (0, pad), value=S)
+    bhi = torch.nn.functional.pad(torch.where(live, hi, torch.zeros_like(hi)), (0, pad), value=0)
+    bhi = bhi.view(B, nb, _DOC_BLOCK).amax(2) if S else bhi.view(B, nb)
+    blo = torch.minimum(blo.view(B, nb, _DOC_BLOCK).amin(2), bhi) if S else blo.view(B, nb)
+    flat = torch.cat([r.reshape(-1), torch.stack([blo, bhi], 2).reshape(-1)])
+    n = B * S * 2
+    return DocRange(flat[:n].view(B, S, 2), flat[n:].view(B, nb, 2), flat)
+
+
+def doc_range_from_segment_ids(segment_ids: torch.Tensor, check: bool = False) -> DocRange:
+    """Document spans (``DocRange``) of integer ``[B, S]`` segment ids: 0 marks padding, each
+    document is a contiguous run of one non-zero id, and an id does not come back in a row after a
+    different id; pads may sit at the front, at the end or between documents.  Runs on the ids'
+    device with no host synchronisation, so a captured step can call it on its static input.
+
+    Ids that break the rule are not detected: every run counts as a document of its own.
+    ``check=True`` synchronises and raises ``ValueError`` for an id that reappears in a row."""
+    if segment_ids.dim() != 2:
+        raise ValueError(f"segment_ids must be [B, S], got {tuple(segment_ids.shape)}")
+    if segment_ids.dtype.is_floating_point or segment_ids.dtype == torch.bool:
+        raise ValueError(f"segment_ids must be an integer tensor, got {segment_ids.dtype}")
+    B, S = segment_ids.shape
+    dev = segment_ids.device
+    if S == 0:
+        return _doc_pack(torch.zeros((B, 0, 2), dtype=torch.int32, device=dev))
+    seg = segment_ids
+    live = seg != 0
+    edge = seg[:, 1:] != seg[:, :-1]
+    one = torch.ones((B, 1), dtype=torch.bool, device=dev)
+    first = live & torch.cat([one, edge], 1)          # first token of a run
+    last = live & torch.cat([edge, one], 1)           # last token of a run
+    idx = torch.arange(S, device=dev, dtype=torch.int64).expand(B, S)
+    # lo = the latest run start at or before i; hi = the earliest run end at or after i, + 1
+    lo = torch.where(first, idx, torch.zeros_like(idx)).cummax(1).values
+    hi = torch.where(last, idx + 1, torch.full_like(idx, S)).flip(1).cummin(1).values.flip(1)
+    zero = torch.zeros_like(idx)
+    if check:
+        ids, rows = seg[first], idx.new_tensor(range(B)).view(B, 1).expand(B, S)[first]
+        pairs = torch.stack([rows, ids.to(torch.int64)], 1)
+        if pairs.shape[0] != torch.unique(pairs, dim=0).shape[0]:
+            raise ValueError("segment_ids: an id reappears in a row after a different id or a pad -- "
+                             "only contiguous documents map to document spans")
+    return _doc_pack(torch.stack([torch.where(live, lo, zero), torch.where(live, hi, zero)], 2))
+
+
+def doc_position_ids(doc_range: DocRange | torch.Tensor) -> torch.Tensor:
+    """Position of every token inside its document, int64 [B, S]: i - lo_i, 0 for a pad."""
+    r = doc_range.ranges if isinstance(doc_range, DocRange) else doc_range
+    S = r.shape[1]
+    i = torch.arange(S, device=r.device, dtype=torch.int64).view(1, S)
+    lo, hi = r[..., 0].to(torch.int64), r[..., 1].to(torch.int64)
+    return torch.where(hi > lo, i - lo, torch.zeros_like(lo))
+
+
+def _doc_ranges(doc_range, B, S) -> torch.Tensor:
+    r = doc_range.ranges if isinstance(doc_range, DocRange) else doc_range
+    if tuple(r.shape) != (B, S, 2):
+        raise ValueError(f"doc_range must be [B, S, 2] = [{B}, {S}, 2], got {tuple(r.shape)}")
+    return r
+
+
+def _doc_mask(doc_range, B, S, device):
+    """[B, 1, S, S] bool, True where key j lies OUTSIDE query i's document span."""
+    r = _doc_ranges(doc_range, B, S).to(device=device, dtype=torch.int64)
+    j = torch.arange(S, device=device).view(1, 1, S)
+    return ((j < r[:, :, :1]) | (j >= r[:, :, 1:])).view(B, 1, S, S)
+
+
+def _exclusive(key_range, doc_range):
+    if key_range is not None and doc_range is not None:
+        raise ValueError("key_range and doc_range are mutually exclusive (padding is an empty span of doc_range)")
+
+
 def _range_mask(key_range, B, S, device):
     """[B, 1, 1, S] bool, True where the key is OUTSIDE its sequence's range."""
     kr = key_range.to(device=device, dtype=torch.int64).view(B, 2)
@@ -91,7 +194,8 @@ def _probs(s, lse):
     return torch.exp(s - lse.masked_fill(lse == float("-inf"), 0.0))
 
 
-def _scores(q, k, scale, causal, slopes, key_range=None):
+def _scores(q, k, scale, causal, slopes, key_range=None, doc_range=None):
+    _exclusive(key_range, doc_range)
     c = _cdt(q)
     s = torch.matmul(q.to(c), k.to(c).transpose(-1, -2)) * scale
     S = q.shape[2]
@@ -102,6 +206,8 @@ def _scores(q, k, scale, causal, slopes, key_range=None):
         s = s.masked_fill(m, float("-inf"))
     if key_range is not None:
         s = s.masked_fill(_range_mask(key_range, q.shape[0], S, s.device), float("-inf"))
+    if doc_range is not None:
+        s = s.masked_fill(_doc_mask(doc_range, q.shape[0], S, s.device), float("-inf"))
     return s
 
 
@@ -111,10 +217,10 @@ def _drop_mask(B, H, S, p, rng, sid, device):
 
 
 def attn_fwd_ref(qkv, B, S, H, D, causal=False, slopes=None, p=0.0, rng: RngState | None = None, sid=0,
-                 scale=None, key_range=None):
+                 scale=None, key_range=None, doc_range=None):
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     q, k, v = _split(qkv, B, S, H, D)
-    s = _scores(q, k, scale, causal, slopes, key_range)
+    s = _scores(q, k, scale, causal, slopes, key_range, doc_range)
     lse = torch.logsumexp(s, -1)       # -inf for a row without a key
     prob = _probs(s, lse)
     if p > 0:
@@ -124,10 +230,10 @@ def attn_fwd_ref(qkv, B, S, H, D, causal=False, slopes=None, p=0.0, rng: RngStat
 
 
 def attn_bwd_ref(dctx, qkv, ctx, lse, B, S, H, D, causal=False, slopes=None, p=0.0, rng=None, sid=0, scale=None,
-                 key_range=None):
+                 key_range=None, doc_range=None):
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     q, k, v = _split(qkv, B, S, H, D)
-    s = _scores(q, k, scale, causal, slopes, key_range)
+    s = _scores(q, k, scale, causal, slopes, key_range, doc_range)
     prob = _probs(s, lse)
     c = s.dtype
     do = dctx.view(B, S, H, D).transpose(1, 2).to(c)
@@ -185,9 +291,10 @@ def fused_bwd_built() -> bool:
     return _lib.has("dtd_attn_fused_bwd_built") and bool(_lib.lib().dtd_attn_fused_bwd_built())
 
 
-def fused_bwd_applies(S: int, D: int, causal: bool, slopes, key_range=None) -> bool:
-    """Whether ``attn_bwd`` may take a one-kernel form; never with a key range (split pair only)."""
-    return (key_range is None and D == 64 and not causal and slopes is None and S % 128 == 0 and S <= 512
+def fused_bwd_applies(S: int, D: int, causal: bool, slopes, key_range=None, doc_range=None) -> bool:
+    """Whether ``attn_bwd`` may take a one-kernel form; never with a key range or document spans
+    (split pair only)."""
+    return (key_range is None and doc_range is None and D == 64 and not causal and slopes is None and S % 128 == 0 and S <= 512
             and fused_bwd_built())
 
 
@@ -198,6 +305,21 @@ def _range_arg(key_range: torch.Tensor, B: int, device) -> torch.Tensor:
     if not _lib.has("dtd_attn_fwd_range"):
         raise _lib.KernelError("the kernel library has no ranged attention entry points (stale build)")
     return key_range.to(device=device, dtype=torch.int32).contiguous()
+
+
+def _doc_arg(doc_range, B: int, S: int, device) -> torch.Tensor:
+    """The kernels' doc argument: int32, the [B, S, 2] spans then the [B, ceil(S/128), 2] block
+    bounds, contiguous, on the activations' device.  Bare [B, S, 2] spans get their bounds here."""
+    _doc_ranges(doc_range, B, S)
+    if not _lib.has("dtd_attn_fwd_doc"):
+        raise _lib.KernelError("the kernel library has no document-masked attention entry points (stale build)")
+    if not isinstance(doc_range, DocRange):
+        doc_range = _doc_pack(doc_range.to(device))
+    flat = doc_range.flat.to(device=device, dtype=torch.int32).contiguous()
+    nb = (S + _DOC_BLOCK - 1) // _DOC_BLOCK
+    if flat.numel() != 2 * B * (S + nb):
+        raise ValueError(f"doc_range.flat must hold 2 * B * (S + ceil(S/128)) = {2 * B * (S + nb)} ints, got {flat.numel()}")
+    return flat
 
 
 def kernel_supported(qkv: torch.Tensor, D: int) -> bool:
@@ -297,25 +419,31 @@ def attn_masks_async(B, S, H, D, p, rng: RngState, sid, device) -> PendingMasks 
 
 
 def attn_fwd(qkv, B, S, H, D, causal=False, slopes=None, p=0.0, rng: RngState | None = None, sid=0,
-             masks: PendingMasks | None = None, key_range: torch.Tensor | None = None):
+             masks: PendingMasks | None = None, key_range: torch.Tensor | None = None,
+             doc_range: DocRange | torch.Tensor | None = None):
     """Returns (ctx [B*S, H*D], lse [B, H, S] fp32, masks).  ``masks`` holds the dropout keep
     bits for the backward ([2, B*H*S*ceil(S/32)] int32 on the kernel path, None otherwise);
     pass the ``attn_masks_async`` result to reuse masks generated ahead on a side stream.
 
     ``key_range``: optional int32 [B, 2] per-sequence key ranges (module docstring).  The bf16
     kernels skip the key tiles outside a range.  fp32 inputs with a range take the math reference
-    (the reference-precision fp32 kernels know no range)."""
-    if key_range is not None and qkv.dtype == torch.float32:
+    (the reference-precision fp32 kernels know no range).
+
+    ``doc_range``: optional document spans of a packed batch (``DocRange``, or the bare int [B, S, 2]
+    spans), exclusive with ``key_range``.  The bf16 kernels visit only the key tiles between each
+    128-query block's bounds; fp32 inputs take the math reference, as with a key range."""
+    _exclusive(key_range, doc_range)
+    if (key_range is not None or doc_range is not None) and qkv.dtype == torch.float32:
         if masks is not None:    # keep bits generated ahead for the fp32 kernels: unused, but join
             torch.cuda.current_stream(qkv.device).wait_event(masks.event)   # before their buffer is freed
-        ctx, lse = attn_fwd_ref(qkv, B, S, H, D, causal, slopes, p, rng, sid, key_range=key_range)
+        ctx, lse = attn_fwd_ref(qkv, B, S, H, D, causal, slopes, p, rng, sid, key_range=key_range, doc_range=doc_range)
         return ctx, lse, None
     if f32_kernel_supported(qkv, D):
         return _attn_fwd_f32(qkv, B, S, H, D, causal, slopes, p, rng, sid, masks)
     if not kernel_supported(qkv, D):
         if qkv.is_cuda and qkv.dtype == torch.bfloat16 and _lib.has("dtd_attn_fwd") is False:
             _warn_once()
-        ctx, lse = attn_fwd_ref(qkv, B, S, H, D, causal, slopes, p, rng, sid, key_range=key_range)
+        ctx, lse = attn_fwd_ref(qkv, B, S, H, D, causal, slopes, p, rng, sid, key_range=key_range, doc_range=doc_range)
         return ctx, lse, None
     qkv = qkv.contiguous()
     ctx = torch.empty((B * S, H * D), dtype=qkv.dtype, device=qkv.device)
@@ -336,7 +464,10 @@ def attn_fwd(qkv, B, S, H, D, causal=False, slopes=None, p=0.0, rng: RngState | 
     args = (base, base + H * D * es, base + 2 * H * D * es, ctx.data_ptr(), lse.data_ptr(),
             _lib.ptr(sl), _lib.ptr(masks), B, S, H, D, ld, H * D, int(causal), 1.0 / math.sqrt(D), float(p),
             rng_ptr, sid)
-    if key_range is None:
+    if doc_range is not None:
+        doc = _doc_arg(doc_range, B, S, qkv.device)
+        _lib.call("dtd_attn_fwd_doc", *args, doc.data_ptr(), _lib.stream())
+    elif key_range is None:
         _lib.call("dtd_attn_fwd", *args, _lib.stream())
     else:
         kr = _range_arg(key_range, B, qkv.device)
@@ -345,17 +476,23 @@ def attn_fwd(qkv, B, S, H, D, causal=False, slopes=None, p=0.0, rng: RngState | 
 
 
 def attn_bwd(dctx, qkv, ctx, lse, B, S, H, D, causal=False, slopes=None, p=0.0, rng=None, sid=0, masks=None,
-             dbias=None, key_range: torch.Tensor | None = None):
+             dbias=None, key_range: torch.Tensor | None = None,
+             doc_range: DocRange | torch.Tensor | None = None):
     """Returns dqkv [B*S, 3*H*D] in the qkv layout.  ``dbias`` = (dst, acc): also writes the
     column sums of dqkv (the qkv projection's bias gradient) -- on the kernel path as per-wave
     partials from the dQ / dK,dV epilogues (no extra pass over dqkv).
 
     ``key_range``: the forward's ranges.  Keys outside a range get zero dK / dV; the bf16 path
     runs the split dQ + dK/dV kernels (never a one-kernel form) and skips the key tiles / key
-    blocks outside the range.  fp32 inputs with a range take the math reference."""
+    blocks outside the range.  fp32 inputs with a range take the math reference.
+
+    ``doc_range``: the forward's document spans.  Pad keys get zero dK / dV and pad queries zero dQ;
+    the split kernels visit only the key tiles (dQ) / query tiles (dK/dV) between each block's bounds."""
     from . import functional as Fx
-    if key_range is not None and qkv.dtype == torch.float32:
-        dqkv = attn_bwd_ref(dctx, qkv, ctx, lse, B, S, H, D, causal, slopes, p, rng, sid, key_range=key_range)
+    _exclusive(key_range, doc_range)
+    if (key_range is not None or doc_range is not None) and qkv.dtype == torch.float32:
+        dqkv = attn_bwd_ref(dctx, qkv, ctx, lse, B, S, H, D, causal, slopes, p, rng, sid, key_range=key_range,
+                            doc_range=doc_range)
         if dbias is not None:
             Fx.bias_grad(dqkv, *dbias)
         return dqkv
@@ -365,7 +502,8 @@ def attn_bwd(dctx, qkv, ctx, lse, B, S, H, D, causal=False, slopes=None, p=0.0, 
             Fx.bias_grad(dqkv, *dbias)
         return dqkv
     if not kernel_supported(qkv, D):
-        dqkv = attn_bwd_ref(dctx, qkv, ctx, lse, B, S, H, D, causal, slopes, p, rng, sid, key_range=key_range)
+        dqkv = attn_bwd_ref(dctx, qkv, ctx, lse, B, S, H, D, causal, slopes, p, rng, sid, key_range=key_range,
+                            doc_range=doc_range)
         if dbias is not None:
             Fx.bias_grad(dqkv, *dbias)
         return dqkv
@@ -383,7 +521,10 @@ def attn_bwd(dctx, qkv, ctx, lse, B, S, H, D, causal=False, slopes=None, p=0.0, 
     args = (qb, qb + H * D * es, qb + 2 * H * D * es, ctx.data_ptr(), dctx.data_ptr(),
             lse.data_ptr(), delta.data_ptr(), _lib.ptr(masks), gb, gb + H * D * es, gb + 2 * H * D * es,
             _lib.ptr(sl), B, S, H, D, ld, H * D, int(causal), 1.0 / math.sqrt(D), float(p), _lib.ptr(part))
-    if key_range is None:
+    if doc_range is not None:
+        doc = _doc_arg(doc_range, B, S, qkv.device)
+        _lib.call("dtd_attn_bwd_doc", *args, doc.data_ptr(), _lib.stream())
+    elif key_range is None:
         _lib.call("dtd_attn_bwd", *args, _lib.stream())
     else:
         kr = _range_arg(key_range, B, qkv.device)

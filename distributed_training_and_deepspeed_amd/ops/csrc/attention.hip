@@ -30,7 +30,10 @@
 // counter RNG (mask index ((b*H+h)*S + q)*S + key, regenerated in backward), arbitrary S
 // (bounds-masked), head_dim 64 or 128, and an optional key range [lo, hi) per sequence (the
 // key-padding mask of a padded batch: keys outside it score -inf and their tiles are skipped --
-// the RANGE instantiations, reached through dtd_attn_fwd_range / dtd_attn_bwd_range only).  q/k/v/o are strided views (row stride `ld`) into the
+// the RANGE instantiations, reached through dtd_attn_fwd_range / dtd_attn_bwd_range only), or an
+// optional document span [lo, hi) per position (sequence packing: attention is block-diagonal over
+// the documents of a row, and each workgroup visits only the tiles between its block's bounds -- the
+// DOC instantiations, reached through dtd_attn_fwd_doc / dtd_attn_bwd_doc only).  q/k/v/o are strided views (row stride `ld`) into the
 // fused [B*S, 3*H*D] projection output, so no transpose/copy kernels are needed.
 #include <stdio.h>
 #include <type_traits>
@@ -178,6 +181,11 @@ struct FwdArgs {
   int B, S, H, ld, ldo, causal, W;
   float scale, p, thr;
   const int* kv_range;    // optional [B][2] = (lo, hi): key j of sequence b takes part iff lo <= j < hi (RANGE kernels)
+  // DOC kernels (sequence packing) read another array through the same field, so that the argument
+  // block -- and with it the other instantiations' register figures -- stays as it was: [B][S][2] =
+  // half-open span (lo, hi) of each position's document ((0, 0) for a pad), followed at once by
+  // [B][ceil(S/128)][2] = (min lo, max hi) over each 128-position block's non-empty rows ((0, 0) for
+  // a block without one).
 };
 
 // Key range of sequence b, clamped to [0, S]; b is workgroup-uniform, so both are scalar loads and
@@ -186,6 +194,28 @@ __device__ __forceinline__ void load_range(const int* kv_range, int b, int S, in
   lo = __builtin_amdgcn_readfirstlane(min(max(kv_range[2 * b], 0), S));
   hi = __builtin_amdgcn_readfirstlane(max(min(kv_range[2 * b + 1], S), 0));
 }
+// Document bounds of 128-position block `blk` of sequence b (DOC kernels): load_range on the
+// [B][nblk][2] block array behind the [B][S][2] spans -- one scalar load pair, wave-uniform loop bounds.
+__device__ __forceinline__ void load_block_range(const int* doc, int B, int b, int nblk, int blk, int S, int& lo, int& hi) {
+  load_range(doc + (size_t)B * S * 2, b * nblk + blk, S, lo, hi);
+}
+// Document span of this lane's position (its query in the forward / dQ, its key in dK/dV), as
+// (lo, length) clamped into [0, S]: position j is inside iff (unsigned)(j - lo) < (unsigned)len, one
+// subtract and one compare.  Positions past S read (0, 0) through the bounded resource: an empty
+// span, like a pad's.
+struct DocSpan {
+  int lo, len;
+  __device__ __forceinline__ bool has(int j) const { return (unsigned)(j - lo) < (unsigned)len; }
+  // the span covers [j0, j0 + n)
+  __device__ __forceinline__ bool covers(int j0, int n) const { return j0 >= lo && j0 + n - lo <= len; }
+};
+// what the kernels without document spans hold in its place: nothing
+struct NoSpan {
+  __device__ __forceinline__ NoSpan& operator=(const DocSpan&) { return *this; }   // (only in discarded branches)
+  __device__ __forceinline__ bool has(int) const { return true; }
+  __device__ __forceinline__ bool covers(int, int) const { return true; }
+};
+template <bool DOC> using SpanOf = std::conditional_t<DOC, DocSpan, NoSpan>;
 
 // Dropout keep-masks for one attention call, generated once in a VALU-only pass at full
 // occupancy (instead of re-hashing inside the MFMA-bound forward, dK/dV and dQ kernels) and
@@ -362,6 +392,13 @@ __device__ __forceinline__ float load_stat(__amdgpu_buffer_rsrc_t rs, int off) {
 
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+// DocSpan of position `pos` of sequence b: one 8-byte load per lane, in the prologue
+__device__ __forceinline__ DocSpan load_span(const int* doc_range, int b, int S, int pos) {
+  const __amdgpu_buffer_rsrc_t rs = bounded_rsrc(doc_range + (size_t)b * S * 2, (uint32_t)S * 8u);
+  const u32x2 v = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rs, pos * 8, 0, 0));
+  const int lo = min(max((int)v.x, 0), S), hi = max(min((int)v.y, S), 0);
+  return DocSpan{lo, max(hi - lo, 0)};
+}
 // Epilogue store of a wave's 32 rows x D columns from NDB 32x32 accumulators (lane r = row, its
 // half-wave hh holds columns 8 k + 4 hh .. + 3 of column group k = 4 d + gq): bf16(acc * scale),
 // 16 bytes per lane per store.  One v_permlane32_swap per dword (vdst = group k, src = group
@@ -457,234 +494,21 @@ struct TileLoader {
 // RANGE: per-sequence key range a.kv_range (key-padding mask): keys outside [lo, hi) score -inf
 // and only the key tiles floor(lo / BN) .. ceil(min(hi, causal end) / BN) - 1 are visited.  A row
 // left without a key (lo >= hi, or causal with q < lo) ends with m = -inf, l = 0: ctx 0, lse -inf.
+// DOC (sequence packing, instead of RANGE): every lane holds the document span of its query (the
+// spans a.kv_range then points to): key j takes part iff it lies inside it.  The tile range comes
+// from the 128-query block's bounds (the array behind the spans) exactly as RANGE's comes from the
+// sequence's; a tile is masked when some lane's span does not cover it (a wave-uniform vote).  A
+// block without a non-empty row runs no tile and writes the empty rows.  The DOC form is a kernel of its own name, attn_fwd_doc_kernel,
+// so that the instantiations without it keep their symbols; both include attention_fwd_body.h.
 template <int D, int OCC, int BN, int RING, bool PK = false, bool RANGE = false>
 __global__ void __launch_bounds__(256, OCC) attn_fwd_kernel(FwdArgs a) {
-  // K rows (ds_read_b128, 4x16-lane groups): pitch D+8 puts the 16 rows of a group on 16
-  // distinct 4-bank windows.  V (ds_read_b64_tr_b16, rows rr = 0..3 x column halves g = 0,1 per
-  // 32-lane group): pitch D+32 (48 / 80 dwords = 16 mod 64) places the eight 8-dword windows
-  // at distinct multiples of 8 mod 64 -- D+8 aliased rows 0/2 and 1/3 (2-way conflicts).
-  constexpr int KP = D + 8, VP = D + 32, NC = D / 16, NDB = D / 32, NKB = BN / 32;
-  __shared__ __attribute__((aligned(16))) bf16 Ks[2][BN * KP];
-  __shared__ __attribute__((aligned(16))) bf16 Vs[2][BN * VP];
-
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), hh = lane >> 5,
-            r = lane & 31;
-  int tx, ty;
-  xcd_tile(tx, ty);
-  const int bh = ty, b = bh / a.H, h = bh % a.H;
-  const int S = a.S;
-  const int qblk = tx * 128, q0 = qblk + w * 32;
-  const int q = q0 + r;
-  const bool qvalid = q < S;
-  const float sl2 = a.slopes ? a.slopes[h] * kLog2e : 0.f;
-  const float sc2 = a.scale * kLog2e;
-  const bool drop = a.maskA != nullptr;
-  const float inv_keep = drop ? 1.f / (1.f - a.p) : 1.f;
-  const RowSrc ksrc = row_src<D>(a.k + (size_t)b * S * a.ld + h * D, a.ld, S);
-  const RowSrc vsrc = row_src<D>(a.v + (size_t)b * S * a.ld + h * D, a.ld, S);
-  // dropout: this wave's 32 queries are one query word of the key-major layout, so the keep masks
-  // of a 32-key block are 16 aligned 64-bit words (lm_pos) -- scalar loads, one v_cndmask per
-  // score.  A one-dword-per-lane vector load of the same 64 words a tile ahead pulls them into L2.
-  const int Sp = 32 * a.W;
-  // keep-word addresses stay inside the real mask buffer: the row is clamped to the plane (a wave
-  // whose queries lie past S still forms it) and each block's offset to the row (keep_off)
-  const uint32_t* mrow = drop ? a.maskB + ((size_t)bh * a.W + min(q0 >> 5, a.W - 1)) * Sp : nullptr;
-  const __amdgpu_buffer_rsrc_t mrs = bounded_rsrc(drop ? (const void*)mrow : (const void*)a.lse, drop ? (uint32_t)Sp * 4u : 0u);
-
-  bf16x8 qf[NC];
-  {
-    const bf16* qp = a.q + ((size_t)(b * S + (qvalid ? q : 0)) * a.ld + h * D);
-#pragma unroll
-    for (int c = 0; c < NC; ++c) qf[c] = qvalid ? *reinterpret_cast<const bf16x8*>(qp + 16 * c + 8 * hh) : bf16x8{};
-  }
-  f32x16 oacc[NDB];
-#pragma unroll
-  for (int d = 0; d < NDB; ++d) oacc[d] = f32x16{};
-  float m = -INFINITY, l = 0.f;
-
-  // key range of this sequence (RANGE): (0, S) otherwise; khi replaces S as the end of the keys
-  int klo = 0, khi = S;
-  if constexpr (RANGE) load_range(a.kv_range, b, S, klo, khi);
-  const int kend = a.causal ? min(khi, qblk + 128) : khi;
-  const int nt = (kend + BN - 1) / BN;
-  // first tile of the range; with no tile to run (t0 >= nt) the loop below is skipped and the
-  // epilogue writes the empty rows.  `last` clamps the ring's look-ahead loads to a tile >= t0.
-  const int t0 = RANGE ? klo / BN : 0;
-  const int last = RANGE ? max(nt - 1, t0) : nt - 1;
-  // K/V tiles stream through a 2-deep register ring: tile t+2's global loads are issued while
-  // tile t is computed and written to LDS only at the end of tile t+1, so each load has two
-  // tiles of compute to arrive (one tile of MFMA/softmax work is shorter than an HBM round trip).
-  // The dropout keep words (one per 32 keys) ride along in the same ring.
-  // RING = 1: one register set (tile t+1 in flight during tile t) -- 16 fewer VGPRs at BN = 64,
-  // which is what 3 waves per SIMD needs.
-  TileLoader<D, BN> kl0, vl0, kl1r, vl1r;
-  TileLoader<D, BN>& kl1 = RING == 2 ? kl1r : kl0;
-  TileLoader<D, BN>& vl1 = RING == 2 ? vl1r : vl0;
-  uint32_t pf0 = 0, pf1r = 0;   // L2 prefetch of keep words (value unused)
-  uint32_t& pf1 = RING == 2 ? pf1r : pf0;
-  auto prefetch_words = [&](int k0, uint32_t& out) {
-    asm volatile("" :: "v"(out));   // retire the previous prefetch held in this register
-    out = __builtin_amdgcn_raw_buffer_load_b32(mrs, lane * 4, k0 * 4, 0);
-  };
-  kl0.load(ksrc, t0 * BN);
-  vl0.load(vsrc, t0 * BN);
-  kl0.store(Ks[0], KP);
-  vl0.store(Vs[0], VP);
-  {
-    const int k1 = min(t0 + 1, last) * BN, k2 = min(t0 + 2, last) * BN;
-    kl1.load(ksrc, k1); vl1.load(vsrc, k1); prefetch_words(k1, pf1);
-    if constexpr (RING == 2) { kl0.load(ksrc, k2); vl0.load(vsrc, k2); prefetch_words(k2, pf0); }
-  }
-  __syncthreads();
-  // SET = register set holding tile t+1 (t - t0 even -> 1, odd -> 0)
-  auto tile = [&](auto set_c, int t) {
-    constexpr int SET = decltype(set_c)::value;
-    TileLoader<D, BN>& kn = SET ? kl1 : kl0;
-    TileLoader<D, BN>& vn = SET ? vl1 : vl0;
-    uint32_t& pfn = SET ? pf1 : pf0;
-    const int buf = (t - t0) & 1, k0 = t * BN;
-    const bf16* K = Ks[buf];
-    const bf16* V = Vs[buf];
-    // keep masks of the tile's first 32-key block: issued ahead of the score MFMAs (their L2
-    // round trip hides under the QK^T / softmax work); the next block's after this one's selects
-    uint64_t mk[16];
-    auto load_masks = [&](int kb) {
-      const cu64* mp = (const cu64*)(uintptr_t)(mrow + keep_off(k0 + kb * 32, Sp));
-#pragma unroll
-      for (int i = 0; i < 16; ++i) mk[i] = mp[i];
-    };
-    f32x16 sacc[NKB];
-#pragma unroll
-    for (int kb = 0; kb < NKB; ++kb) {
-      f32x16 acc = f32x16{};
-#pragma unroll
-      for (int c = 0; c < NC; ++c)
-        acc = mfma32(*reinterpret_cast<const bf16x8*>(&K[(kb * 32 + r) * KP + 16 * c + 8 * hh]), qf[c], acc);
-      sacc[kb] = acc;
-    }
-    // the first block's keep masks: issued once the score MFMAs' LDS operands are consumed (an
-    // outstanding scalar load makes every later LDS wait a full lgkmcnt(0)), landing under the
-    // max / exp work
-    if (drop) load_masks(0);
-    // log2-domain scores.  Fast path (no ALiBi, interior tile): the row max is taken on the raw
-    // accumulator (scale > 0) and the scale is folded into the exponent's FMA -- 4 VALU per score
-    // incl. the running sum, vs 10+ with a per-element scale/bias/mask pass.
-    // (RANGE: khi <= S stands for the end of the keys, and the tile holding klo is masked too)
-    const bool needmask = (k0 + BN > khi) || (RANGE && k0 < klo) || (a.causal && k0 + BN - 1 > q0);
-    const bool slow = needmask || sl2 != 0.f;
-    float tmax = -INFINITY;
-    if (slow) {
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int key = k0 + kb * 32 + crow(i, hh);
-          float s = fmaf(sacc[kb][i], sc2, sl2 * (float)key);
-          if (needmask && (key >= khi || (RANGE && key < klo) || (a.causal && key > q))) s = -INFINITY;
-          sacc[kb][i] = s;
-          tmax = fmaxf(tmax, s);
-        }
-    } else {
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) tmax = fmaxf(tmax, sacc[kb][i]);
-      tmax *= sc2;
-    }
-    tmax = xhalf_max(tmax);
-    // defer-max (wave-uniform decision): keep the running max unless some row's tile max
-    // exceeds it by > kRescaleThr; the previous tile's P.V is complete, so O and l are the
-    // only terms at the old scale.  m = -inf (first tile / fully masked so far) -> alpha 0.
-    // (A row with every key masked so far has tmax = m = -inf: the NaN difference takes the
-    // rescale, which leaves m = -inf, l = 0, O = 0.)
-    if (!__all(tmax - m <= a.thr)) {
-      const float mnew = fmaxf(m, tmax);
-      const float alpha = m == -INFINITY ? 0.f : fexp2(m - mnew);
-      m = mnew;
-      l *= alpha;
-#pragma unroll
-      for (int d = 0; d < NDB; ++d) oacc[d] *= alpha;
-    }
-    const float mexp = m == -INFINITY ? 0.f : m;
-    const float msc = slow ? 1.f : sc2;
-    // l stays a per-half partial (both halves share m, hence every rescale); the two halves
-    // are combined once in the epilogue.  Four independent partial sums shorten the add chain.
-    if constexpr (PK) {
-      const f32x2 msc2 = pk2(msc, msc), nm2 = pk2(-mexp, -mexp);
-      f32x2 ps2[2];
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-        for (int i = 0; i < 16; i += 2) {
-          const f32x2 x = pk_fma(pk2(sacc[kb][i], sacc[kb][i + 1]), msc2, nm2);
-          const f32x2 pv = pk2(fexp2(x.x), fexp2(x.y));
-          const int j = (i >> 1) & 1;
-          ps2[j] = (kb == 0 && i < 4) ? pv : ps2[j] + pv;
-          sacc[kb][i] = pv.x;
-          sacc[kb][i + 1] = pv.y;
-        }
-      l += (ps2[0].x + ps2[0].y) + (ps2[1].x + ps2[1].y);
-    } else {
-      float ps[4];
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const float pv = fexp2(fmaf(sacc[kb][i], msc, -mexp));
-          ps[i & 3] = (kb == 0 && i < 4) ? pv : ps[i & 3] + pv;   // no "+ 0" adds (-0 semantics keep them)
-          sacc[kb][i] = pv;
-        }
-      l += (ps[0] + ps[1]) + (ps[2] + ps[3]);
-    }
-    if (drop) {
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb) {
-        if (kb > 0) load_masks(kb);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) sacc[kb][i] = sel_keep(sacc[kb][i], mk[i]);
-      }
-    }
-    // O^T += V^T . P^T: the score accumulator is the B operand; V^T comes from transposed reads
-#pragma unroll
-    for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        bf16x8 pf;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) pf[j] = (bf16)sacc[kb][8 * s + j];
-#pragma unroll
-        for (int d = 0; d < NDB; ++d) oacc[d] = mfma32(tr_operand(V, VP, kb * 32 + 16 * s, d * 32, lane), pf, oacc[d]);
-      }
-    if (t + 1 < nt) {
-      kn.store(Ks[buf ^ 1], KP);
-      vn.store(Vs[buf ^ 1], VP);
-      // tile t+1+RING (clamped to the last tile: a harmless reload keeps the issue unconditional)
-      const int kf = min(t + 1 + RING, nt - 1) * BN;
-      kn.load(ksrc, kf);
-      vn.load(vsrc, kf);
-      prefetch_words(kf, pfn);
-    }
-    __syncthreads();
-  };
-  for (int t = t0; t < nt; t += 2) {
-    tile(std::integral_constant<int, 1>{}, t);
-    if (t + 1 < nt) tile(std::integral_constant<int, 0>{}, t + 1);
-  }
-  l = xhalf_sum(l);
-  if (!qvalid) return;
-  const float inv_l = l > 0.f ? inv_keep / l : 0.f;   // dropout 1/(1-p) folded in here
-  bf16* op = a.o + (size_t)(b * S + q) * a.ldo + h * D;
-#pragma unroll
-  for (int d = 0; d < NDB; ++d)
-#pragma unroll
-    for (int gq = 0; gq < 4; ++gq) {
-      bf16x4 v4;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) v4[t] = (bf16)(oacc[d][4 * gq + t] * inv_l);
-      *reinterpret_cast<bf16x4*>(op + d * 32 + 8 * gq + 4 * hh) = v4;
-    }
-  // (a row without a key: m = -inf, l = 0 -> -inf)
-  if (hh == 0) a.lse[(size_t)bh * S + q] = (m + log2f(l)) * kLn2;
+  constexpr bool DOC = false;
+#include "attention_fwd_body.h"
+}
+template <int D, int OCC, int BN, int RING>
+__global__ void __launch_bounds__(256, OCC) attn_fwd_doc_kernel(FwdArgs a) {
+  constexpr bool PK = false, RANGE = false, DOC = true;
+#include "attention_fwd_body.h"
 }
 
 // Software-pipelined forward (D = 64; DTD_ATTN_FWD=pipe): the score MFMAs of K/V tile t+1 are
@@ -877,6 +701,7 @@ struct BwdArgs {
   // one row per (batch, 32-row block of a wave), finished by colsum_finalize
   float* bias_part;
   const int* kv_range;    // optional [B][2] key range per sequence (see FwdArgs; RANGE kernels only)
+                          // (DOC kernels: the document spans and block bounds, see FwdArgs)
 };
 
 // Column sums of a wave's 32 rows x 64 columns of dQ / dK / dV, straight from the accumulators
@@ -923,247 +748,21 @@ __device__ __forceinline__ int colsum_col(int k, int hh) { return (k >> 4) * 32 
 // [lo, hi) runs no query tile and writes zero dK / dV rows and zero bias partials (the gradient
 // buffer is uninitialised); otherwise keys outside the range are masked like keys past S.  Padded
 // query rows take part like any other; a row without a key (lse = -inf) has P = 0.
+// DOC (sequence packing, needs MASK, instead of RANGE): every lane holds the document span of its
+// KEY; the relation is symmetric, so that span is also the set of queries that may see the key and
+// a score is valid iff its query index lies inside it.  Only the query tiles between the block's
+// bounds (the array behind the spans) are visited; a block with empty bounds -- all pads -- writes
+// zeros like a RANGE block outside the range.  Tile order as RANGE's.  (attn_bwd_dkdv_doc_kernel,
+// below.)
 template <int D, int OCC, int BM, bool DROP, bool ALIBI, bool MASK = true, bool RANGE = false>
 __global__ void __launch_bounds__(256, OCC) attn_bwd_dkdv_kernel(BwdArgs a) {
-  static_assert(MASK || !RANGE, "a key range needs the masked form");
-  constexpr bool SWZ = D == 64;                 // swizzled unpadded image (swz64_off)
-  constexpr int QP = SWZ ? D : D + 8, NC = D / 16, NDB = D / 32;
-  // One LDS block, row statistics first: placed after the 72 KiB of Q/dO tiles (BM = 128) their
-  // ds_read offsets exceed the 16-bit immediate and every read needed a VALU address add.
-  struct Smem {
-    float lse_s[2][BM], del_s[2][BM];
-    bf16 Qs[2][BM * QP];
-    bf16 Os[2][BM * QP];
-  };
-  __shared__ __attribute__((aligned(16))) Smem sm;
-  auto& lse_s = sm.lse_s;
-  auto& del_s = sm.del_s;
-  auto& Qs = sm.Qs;
-  auto& Os = sm.Os;
-
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), hh = lane >> 5,
-            r = lane & 31;
-  int tx, ty;
-  if constexpr (RANGE) xcd_tile_grouped(tx, ty);
-  else xcd_tile(tx, ty);
-  const int bh = ty, b = bh / a.H, h = bh % a.H;
-  const int S = a.S;
-  const int kblk = tx * 128;
-  const int key = kblk + w * 32 + r;
-  const bool kvalid = key < S;
-  int klo = 0, khi = S;
-  if constexpr (RANGE) {
-    load_range(a.kv_range, b, S, klo, khi);
-    if (kblk >= khi || kblk + 128 <= klo) {   // block-uniform: no key of this block is in the range
-      if (a.bias_part && D == 64) {
-        float* row = a.bias_part + ((size_t)b * gridDim.x * 4 + (kblk >> 5) + w) * (3 * a.H * D) + h * D + colsum_col(r, hh);
-        row[a.H * D] = 0.f;
-        row[2 * a.H * D] = 0.f;
-      }
-      if (kvalid) {
-        bf16* dkp = a.dk + (size_t)(b * S + key) * a.ld + h * D;
-        bf16* dvp = a.dv + (size_t)(b * S + key) * a.ld + h * D;
-#pragma unroll
-        for (int c = 0; c < D / 16; ++c) {   // both half-waves hold lane r's key: 8 of 16 columns each
-          *reinterpret_cast<bf16x8*>(dkp + 16 * c + 8 * hh) = bf16x8{};
-          *reinterpret_cast<bf16x8*>(dvp + 16 * c + 8 * hh) = bf16x8{};
-        }
-      }
-      return;
-    }
-  }
-  const bool kin = key >= klo && key < khi;     // this lane's key takes part (RANGE)
-  const float sl2 = a.slopes ? a.slopes[h] * kLog2e : 0.f;
-  const float sc2 = a.scale * kLog2e;
-  constexpr bool drop = DROP;
-  const float inv_keep = drop ? 1.f / (1.f - a.p) : 1.f;
-  const float kbias = sl2 * (float)key;   // ALiBi bias of this lane's key (0 without ALiBi)
-  // keep masks: this wave's 32 keys are one key word of the query-major layout A, so a 32-query
-  // block's masks are 16 aligned 64-bit words (lm_pos) -- scalar loads, one v_cndmask per use
-  const int Sp = 32 * a.W;
-  const uint32_t* mrow = drop ? a.maskA + ((size_t)bh * a.W + min((kblk >> 5) + w, a.W - 1)) * Sp : nullptr;
-  const __amdgpu_buffer_rsrc_t mrs = bounded_rsrc(drop ? (const void*)mrow : (const void*)a.lse, drop ? (uint32_t)Sp * 4u : 0u);
-  const RowSrc qsrc = row_src<D>(a.q + (size_t)b * S * a.ld + h * D, a.ld, S);
-  const RowSrc osrc = row_src<D>(a.dout + (size_t)b * S * a.ldo + h * D, a.ldo, S);
-  // row statistics of one (batch, head): bounded resources over the [S] rows, so rows past S read 0
-  const __amdgpu_buffer_rsrc_t lse_rs = bounded_rsrc(a.lse + (size_t)bh * S, (uint32_t)S * 4u);
-  const __amdgpu_buffer_rsrc_t del_rs = bounded_rsrc(a.delta + (size_t)bh * S, (uint32_t)S * 4u);
-
-  bf16x8 kf[NC], vf[NC];
-  load_frags<D>(kf, a.k + (size_t)b * S * a.ld + h * D, a.ld, S, key, hh);   // keys past S: 0
-  load_frags<D>(vf, a.v + (size_t)b * S * a.ld + h * D, a.ld, S, key, hh);
-  f32x16 dk[NDB], dv[NDB];
-#pragma unroll
-  for (int d = 0; d < NDB; ++d) { dk[d] = f32x16{}; dv[d] = f32x16{}; }
-
-  const int qstart = a.causal ? (kblk / BM) * BM : 0;
-  const int nt = (S - qstart + BM - 1) / BM;
-  TileLoader<D, BM> ql, ol;
-  // Raw lse / delta of a query tile, one row per thread of the first BM, issued straight behind the
-  // tile's Q / dO loads with no arithmetic on them: vmcnt retires in order, so a consumer placed
-  // here would drain the whole prefetch it was just issued behind (a full memory round trip at the
-  // head of every tile).  The values are transformed where they go to LDS (store_stats), after the
-  // tile's compute.  Threads past BM get an offset beyond any row: 0, without touching memory.
-  float lse_r = 0.f, del_r = 0.f;
-  const int stat_off = threadIdx.x < BM ? (int)threadIdx.x * 4 : 0x40000000;
-  auto load_stats = [&](int q0) {
-    lse_r = load_stat(lse_rs, q0 * 4 + stat_off);
-    del_r = load_stat(del_rs, q0 * 4 + stat_off);
-  };
-  auto store_stats = [&](int buf, int q0) {
-    if (threadIdx.x < BM) {
-      const bool in = q0 + (int)threadIdx.x < S;
-      float nl = in ? -lse_r * kLog2e : 0.f;       // stored negated: P = 2^fma(s, sc2, -lse)
-      // a row without a key (lse = -inf): P = 2^(s - inf) = 0, not 2^(s + inf)
-      if constexpr (RANGE) nl = nl == INFINITY ? -INFINITY : nl;
-      lse_s[buf][threadIdx.x] = nl;
-      // dS = P (dP - delta); with dropout the kernel forms dS' = (1 - p) dS = Pm dP - P (1 - p) delta
-      // (Pm = P * keep), so delta is stored pre-scaled and dK takes the 1 / (1 - p) at the end
-      del_s[buf][threadIdx.x] = in ? -del_r * (DROP ? 1.f - a.p : 1.f) : 0.f;
-    }
-  };
-  // L2 prefetch of the next query tile's keep words (BM words, value unused)
-  constexpr int NPF = BM / 64;
-  uint32_t pfw[NPF] = {};
-  auto prefetch_words = [&](int q0) {
-#pragma unroll
-    for (int j = 0; j < NPF; ++j) {
-      asm volatile("" :: "v"(pfw[j]));
-      pfw[j] = __builtin_amdgcn_raw_buffer_load_b32(mrs, (lane + 64 * j) * 4, q0 * 4, 0);
-    }
-  };
-  ql.load(qsrc, qstart);
-  ol.load(osrc, qstart);
-  load_stats(qstart);
-  ql.store_bwd(Qs[0], QP);
-  ol.store_bwd(Os[0], QP);
-  store_stats(0, qstart);
-  __syncthreads();
-  for (int t = 0; t < nt; ++t) {
-    const int buf = t & 1, q0 = qstart + t * BM;
-    if (t + 1 < nt) {
-      ql.load(qsrc, q0 + BM);
-      ol.load(osrc, q0 + BM);
-      load_stats(q0 + BM);
-      if (drop) prefetch_words(q0 + BM);
-    }
-    const bf16* Q = Qs[buf];
-    const bf16* O = Os[buf];
-    // one wave per SIMD (OCC 1, 512 registers): unroll the query sub-blocks so the S/dP MFMAs
-    // of sub-block qb+1 can be scheduled under the softmax VALU of qb; at OCC 2 the register
-    // budget keeps the sub-blocks serial
-    constexpr int kQbUnroll = OCC == 1 ? BM / 32 : 1;
-#pragma unroll kQbUnroll
-    for (int qb = 0; qb < BM / 32; ++qb) {
-      f32x16 sacc = f32x16{}, pacc = f32x16{};
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        if constexpr (SWZ) {
-          sacc = mfma32(swz_row_read(Q, qb * 32, r, 2 * c + hh), kf[c], sacc);
-          pacc = mfma32(swz_row_read(O, qb * 32, r, 2 * c + hh), vf[c], pacc);
-        } else {
-          sacc = mfma32(*reinterpret_cast<const bf16x8*>(&Q[(qb * 32 + r) * QP + 16 * c + 8 * hh]), kf[c], sacc);
-          pacc = mfma32(*reinterpret_cast<const bf16x8*>(&O[(qb * 32 + r) * QP + 16 * c + 8 * hh]), vf[c], pacc);
-        }
-      }
-      const int qrow0 = q0 + qb * 32;
-      // block-uniform predicate (a scalar branch, never a per-element one)
-      bool needmask = MASK && ((kblk + 128 > S) || (qrow0 + 32 > S) || (a.causal && kblk + 127 > qrow0));
-      if constexpr (RANGE) needmask = needmask || kblk + 128 > khi || kblk < klo;   // the blocks holding lo / hi
-      // this query block's keep masks (after the S / dP MFMAs consumed their LDS operands)
-      uint64_t mk[16];
-      if constexpr (DROP) {
-        const cu64* mp = (const cu64*)(uintptr_t)(mrow + keep_off(qrow0, Sp));
-#pragma unroll
-        for (int i = 0; i < 16; ++i) mk[i] = mp[i];
-      }
-      // row statistics of this lane's 16 accumulator rows (rows 8g + 4hh + 0..3 are contiguous):
-      // 8 ds_read_b128 issued together instead of 32 dependent scalar LDS reads
-      f32x4 L4[4], D4[4];
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        L4[g] = *reinterpret_cast<const f32x4*>(&lse_s[buf][qb * 32 + 8 * g + 4 * hh]);
-        D4[g] = *reinterpret_cast<const f32x4*>(&del_s[buf][qb * 32 + 8 * g + 4 * hh]);
-      }
-      // P = 2^(s sc2 + kbias - lse): score pairs (i, i+1) share a row group, so the row terms pair up
-      const f32x2 sc2v = pk2(sc2, sc2), kb2 = pk2(kbias, kbias);
-#pragma unroll
-      for (int i = 0; i < 16; i += 2) {
-        f32x2 nl = pk2(L4[i >> 2][i & 3], L4[i >> 2][(i & 3) + 1]);
-        if constexpr (ALIBI) nl += kb2;
-        const f32x2 x = pk_fma(pk2(sacc[i], sacc[i + 1]), sc2v, nl);
-        sacc[i] = fexp2(x.x);
-        sacc[i + 1] = fexp2(x.y);
-      }
-      if (MASK && needmask) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int qq = qrow0 + crow(i, hh);
-          bool ok = kvalid && qq < S && !(a.causal && key > qq);
-          if constexpr (RANGE) ok = ok && kin;
-          sacc[i] = ok ? sacc[i] : 0.f;
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < 16; i += 2) {
-        const f32x2 nd = pk2(D4[i >> 2][i & 3], D4[i >> 2][(i & 3) + 1]);
-        if constexpr (DROP) {
-          // 2 VALU issues per score instead of 3: one keep select (Pm feeds both dV and dS')
-          const f32x2 pm = pk2(sel_keep(sacc[i], mk[i]), sel_keep(sacc[i + 1], mk[i + 1]));
-          const f32x2 u = pk2(sacc[i], sacc[i + 1]) * nd;                 // -P (1 - p) delta
-          const f32x2 ds = pk_fma(pm, pk2(pacc[i], pacc[i + 1]), u);      // dS' = (1 - p) dS
-          pacc[i] = ds.x;
-          pacc[i + 1] = ds.y;
-          sacc[i] = pm.x;                                                 // P*mask (dV)
-          sacc[i + 1] = pm.y;
-        } else {
-          const f32x2 ds = pk2(sacc[i], sacc[i + 1]) * (pk2(pacc[i], pacc[i + 1]) + nd);
-          pacc[i] = ds.x;
-          pacc[i + 1] = ds.y;
-        }
-      }
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        bf16x8 pb, sb;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { pb[j] = (bf16)sacc[8 * s + j]; sb[j] = (bf16)pacc[8 * s + j]; }
-#pragma unroll
-        for (int d = 0; d < NDB; ++d) {
-          if constexpr (SWZ) {
-            dv[d] = mfma32(tr_operand_swz(O, qb * 32 + 16 * s, d * 32, lane), pb, dv[d]);
-            dk[d] = mfma32(tr_operand_swz(Q, qb * 32 + 16 * s, d * 32, lane), sb, dk[d]);
-          } else {
-            dv[d] = mfma32(tr_operand(O, QP, qb * 32 + 16 * s, d * 32, lane), pb, dv[d]);
-            dk[d] = mfma32(tr_operand(Q, QP, qb * 32 + 16 * s, d * 32, lane), sb, dk[d]);
-          }
-        }
-      }
-    }
-    if (t + 1 < nt) {
-      ql.store_bwd(Qs[buf ^ 1], QP);
-      ol.store_bwd(Os[buf ^ 1], QP);
-      store_stats(buf ^ 1, q0 + BM);
-    }
-    __syncthreads();
-  }
-  const float dv_scale = inv_keep;   // the dropped P fed to dV carried keep bits only
-  const float dk_scale = a.scale * inv_keep;   // dS' = (1 - p) dS (see load_stats)
-  if (a.bias_part && D == 64) {
-    float vk[32], vv[32];
-#pragma unroll
-    for (int d = 0; d < NDB; ++d)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {   // the stored (bf16-rounded) values, 0 past S
-        vk[16 * d + i] = kvalid ? (float)(bf16)(dk[d][i] * dk_scale) : 0.f;
-        vv[16 * d + i] = kvalid ? (float)(bf16)(dv[d][i] * dv_scale) : 0.f;
-      }
-    const float sk = colsum32(vk, r), sv = colsum32(vv, r);
-    float* row = a.bias_part + ((size_t)b * gridDim.x * 4 + (kblk >> 5) + w) * (3 * a.H * D) + h * D + colsum_col(r, hh);
-    row[a.H * D] = sk;
-    row[2 * a.H * D] = sv;
-  }
-  store_rows16<NDB>(a.dk + (size_t)(b * S + key) * a.ld + h * D, dk, dk_scale, hh, kvalid);
-  store_rows16<NDB>(a.dv + (size_t)(b * S + key) * a.ld + h * D, dv, dv_scale, hh, kvalid);
+  constexpr bool DOC = false;
+#include "attention_bwd_dkdv_body.h"
+}
+template <int D, int OCC, int BM, bool DROP, bool ALIBI>
+__global__ void __launch_bounds__(256, OCC) attn_bwd_dkdv_doc_kernel(BwdArgs a) {
+  constexpr bool MASK = true, RANGE = false, DOC = true;
+#include "attention_bwd_dkdv_body.h"
 }
 
 // dQ: grid (ceil(S/128), B*H); block 256 = 4 waves x 32 queries (query on the lane, as in the
@@ -1172,201 +771,17 @@ __global__ void __launch_bounds__(256, OCC) attn_bwd_dkdv_kernel(BwdArgs a) {
 // PK: packed-fp32 exp arguments and dS = P (dP - delta) (v_pk_fma_f32 / v_pk_mul_f32)
 // RANGE: key range per sequence, same tile range and masks as the forward (attn_fwd_kernel); a
 // row without a key (lse = -inf) gets P = 0 on every tile, so dQ = 0.
+// DOC: document span per query, block bounds for the tile range, as in attn_fwd_kernel
+// (attn_bwd_dq_doc_kernel, below).
 template <int D, int OCC, int BN, int RING, bool PK = false, bool RANGE = false>
 __global__ void __launch_bounds__(256, OCC) attn_bwd_dq_kernel(BwdArgs a) {
-  constexpr bool SWZ = D == 64;                 // swizzled unpadded K / V images (swz64_off)
-  constexpr int KP = SWZ ? D : D + 8, NC = D / 16, NDB = D / 32;
-  __shared__ __attribute__((aligned(16))) bf16 Ks[2][BN * KP];
-  __shared__ __attribute__((aligned(16))) bf16 Vs[2][BN * KP];
-
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), hh = lane >> 5,
-            r = lane & 31;
-  int tx, ty;
-  xcd_tile(tx, ty);
-  const int bh = ty, b = bh / a.H, h = bh % a.H;
-  const int S = a.S;
-  const int qblk = tx * 128, q0 = qblk + w * 32;
-  const int q = q0 + r;
-  const bool qvalid = q < S;
-  const float sl2 = a.slopes ? a.slopes[h] * kLog2e : 0.f;
-  const float sc2 = a.scale * kLog2e;
-  const bool drop = a.maskA != nullptr;
-  const float inv_keep = drop ? 1.f / (1.f - a.p) : 1.f;
-  const RowSrc ksrc = row_src<D>(a.k + (size_t)b * S * a.ld + h * D, a.ld, S);
-  const RowSrc vsrc = row_src<D>(a.v + (size_t)b * S * a.ld + h * D, a.ld, S);
-  // keep masks as in attn_fwd_kernel: 64-bit lane masks of the key-major layout, scalar loads
-  const int Sp = 32 * a.W;
-  const uint32_t* mrow = drop ? a.maskB + ((size_t)bh * a.W + min(q0 >> 5, a.W - 1)) * Sp : nullptr;
-  const __amdgpu_buffer_rsrc_t mrs = bounded_rsrc(drop ? (const void*)mrow : (const void*)a.lse, drop ? (uint32_t)Sp * 4u : 0u);
-
-  f32x16 dq[NDB];
-#pragma unroll
-  for (int d = 0; d < NDB; ++d) dq[d] = f32x16{};
-
-  // key range, first tile and look-ahead clamp as in attn_fwd_kernel
-  int klo = 0, khi = S;
-  if constexpr (RANGE) load_range(a.kv_range, b, S, klo, khi);
-  const int kend = a.causal ? min(khi, qblk + 128) : khi;
-  const int nt = (kend + BN - 1) / BN;
-  const int t0 = RANGE ? klo / BN : 0;
-  const int last = RANGE ? max(nt - 1, t0) : nt - 1;
-  // K/V tiles + dropout keep words through a 2-deep register ring (see attn_fwd_kernel)
-  constexpr int NKB = BN / 32;
-  // RING = 1: one register set in flight (fewer VGPRs -> 3 waves per SIMD), see attn_fwd_kernel
-  TileLoader<D, BN> kl0, vl0, kl1r, vl1r;
-  TileLoader<D, BN>& kl1 = RING == 2 ? kl1r : kl0;
-  TileLoader<D, BN>& vl1 = RING == 2 ? vl1r : vl0;
-  uint32_t pf0 = 0, pf1r = 0;   // L2 prefetch of keep words (value unused)
-  uint32_t& pf1 = RING == 2 ? pf1r : pf0;
-  auto prefetch_words = [&](int k0, uint32_t& out) {
-    asm volatile("" :: "v"(out));
-    out = __builtin_amdgcn_raw_buffer_load_b32(mrs, lane * 4, k0 * 4, 0);
-  };
-  // Prologue: one memory round trip.  Every load -- K/V tiles t0 and t0 + 1, then this lane's Q,
-  // dO and O fragments and its lse, all branch-free -- is issued before anything waits; tile t0
-  // goes to LDS as soon as it lands (it was issued first: a partial vmcnt) and delta is formed
-  // while the rest arrives.  With RING = 1 tile t0 has a register set of its own, which only
-  // lives here: the accumulators are not live yet, so the prologue stays below the loop's
-  // register peak.
-  bf16x8 qf[NC], of[NC];
-  float lse2, dl;
-  {
-    TileLoader<D, BN> kpr, vpr;
-    TileLoader<D, BN>& kp = RING == 2 ? kl0 : kpr;
-    TileLoader<D, BN>& vp = RING == 2 ? vl0 : vpr;
-    const int k1 = min(t0 + 1, last) * BN, k2 = min(t0 + 2, last) * BN;
-    kp.load(ksrc, t0 * BN);
-    vp.load(vsrc, t0 * BN);
-    kl1.load(ksrc, k1); vl1.load(vsrc, k1); prefetch_words(k1, pf1);
-    bf16x8 ov[NC];
-    load_frags<D>(qf, a.q + (size_t)b * S * a.ld + h * D, a.ld, S, q, hh);       // rows past S: 0
-    load_frags<D>(of, a.dout + (size_t)b * S * a.ldo + h * D, a.ldo, S, q, hh);
-    load_frags<D>(ov, a.o + (size_t)b * S * a.ldo + h * D, a.ldo, S, q, hh);
-    lse2 = load_stat(bounded_rsrc(a.lse + (size_t)bh * S, (uint32_t)S * 4u), q * 4) * kLog2e;
-    // a row without a key: every key it meets is masked below (P = 0 by select); +inf here also
-    // makes the unmasked exponent 2^(s - inf) = 0 instead of 2^(s + inf)
-    if constexpr (RANGE) lse2 = lse2 == -INFINITY ? INFINITY : lse2;
-    asm volatile("" ::: "memory");   // keeps every load above issued ahead of the first wait
-    kp.store_bwd(Ks[0], KP);
-    vp.store_bwd(Vs[0], KP);
-    if constexpr (RING == 2) { kl0.load(ksrc, k2); vl0.load(vsrc, k2); prefetch_words(k2, pf0); }
-    // delta = rowsum(dO * O) of this lane's query, from the dO fragments already in registers and
-    // one O row read (no separate delta pass re-reading dO); stored for the dK/dV kernel, which
-    // runs after this one
-    float part = 0.f;
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) part = fmaf((float)ov[c][j], (float)of[c][j], part);
-    dl = xhalf_sum(part);
-    if (qvalid && hh == 0) a.delta[(size_t)bh * S + q] = dl;
-  }
-  __syncthreads();
-  auto tile = [&](auto set_c, int t) {
-    constexpr int SET = decltype(set_c)::value;
-    TileLoader<D, BN>& kn = SET ? kl1 : kl0;
-    TileLoader<D, BN>& vn = SET ? vl1 : vl0;
-    uint32_t& pfn = SET ? pf1 : pf0;
-    const int buf = (t - t0) & 1, k0 = t * BN;
-    const bf16* K = Ks[buf];
-    const bf16* V = Vs[buf];
-    const bool needmask = !qvalid || (k0 + BN > khi) || (RANGE && k0 < klo) || (a.causal && k0 + BN - 1 > q0);
-#pragma unroll
-    for (int kb = 0; kb < BN / 32; ++kb) {
-      f32x16 sacc = f32x16{}, pacc = f32x16{};
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        if constexpr (SWZ) {
-          sacc = mfma32(swz_row_read(K, kb * 32, r, 2 * c + hh), qf[c], sacc);
-          pacc = mfma32(swz_row_read(V, kb * 32, r, 2 * c + hh), of[c], pacc);
-        } else {
-          sacc = mfma32(*reinterpret_cast<const bf16x8*>(&K[(kb * 32 + r) * KP + 16 * c + 8 * hh]), qf[c], sacc);
-          pacc = mfma32(*reinterpret_cast<const bf16x8*>(&V[(kb * 32 + r) * KP + 16 * c + 8 * hh]), of[c], pacc);
-        }
-      }
-      // this block's keep masks (after the S / dP MFMAs consumed their LDS operands)
-      uint64_t mk[16];
-      if (drop) {
-        const cu64* mp = (const cu64*)(uintptr_t)(mrow + keep_off(k0 + kb * 32, Sp));
-#pragma unroll
-        for (int i = 0; i < 16; ++i) mk[i] = mp[i];
-      }
-      // P = exp2(s*log2e - lse): 2 VALU on interior tiles without ALiBi
-      if (needmask || sl2 != 0.f) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int key = k0 + kb * 32 + crow(i, hh);
-          float pv = fexp2(fmaf(sacc[i], sc2, sl2 * (float)key - lse2));
-          if (needmask && (!qvalid || key >= khi || (RANGE && key < klo) || (a.causal && key > q))) pv = 0.f;
-          sacc[i] = pv;
-        }
-      } else if constexpr (PK) {
-        const f32x2 sc22 = pk2(sc2, sc2), nl2 = pk2(-lse2, -lse2);
-#pragma unroll
-        for (int i = 0; i < 16; i += 2) {
-          const f32x2 x = pk_fma(pk2(sacc[i], sacc[i + 1]), sc22, nl2);
-          sacc[i] = fexp2(x.x);
-          sacc[i + 1] = fexp2(x.y);
-        }
-      } else {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) sacc[i] = fexp2(fmaf(sacc[i], sc2, -lse2));
-      }
-      // dS^T = P * (dP - delta), dP = dropout(dP') (keep bit, 1/(1-p))
-      if constexpr (PK) {
-        const f32x2 ik2 = pk2(drop ? inv_keep : 1.f, drop ? inv_keep : 1.f), nd2 = pk2(-dl, -dl);
-#pragma unroll
-        for (int i = 0; i < 16; i += 2) {
-          f32x2 dp = pk2(pacc[i], pacc[i + 1]);
-          if (drop) dp = pk2(sel_keep(pacc[i], mk[i]), sel_keep(pacc[i + 1], mk[i + 1]));
-          const f32x2 ds = pk2(sacc[i], sacc[i + 1]) * pk_fma(dp, ik2, nd2);
-          sacc[i] = ds.x;
-          sacc[i + 1] = ds.y;
-        }
-      } else if (drop) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) sacc[i] *= fmaf(sel_keep(pacc[i], mk[i]), inv_keep, -dl);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) sacc[i] *= pacc[i] - dl;
-      }
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        bf16x8 sb;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) sb[j] = (bf16)sacc[8 * s + j];
-#pragma unroll
-        for (int d = 0; d < NDB; ++d) {
-          if constexpr (SWZ) dq[d] = mfma32(tr_operand_swz(K, kb * 32 + 16 * s, d * 32, lane), sb, dq[d]);
-          else dq[d] = mfma32(tr_operand(K, KP, kb * 32 + 16 * s, d * 32, lane), sb, dq[d]);
-        }
-      }
-    }
-    if (t + 1 < nt) {
-      kn.store_bwd(Ks[buf ^ 1], KP);
-      vn.store_bwd(Vs[buf ^ 1], KP);
-      // tile t+1+RING (clamped to the last tile: a harmless reload keeps the issue unconditional)
-      const int kf = min(t + 1 + RING, nt - 1) * BN;
-      kn.load(ksrc, kf);
-      vn.load(vsrc, kf);
-      prefetch_words(kf, pfn);
-    }
-    __syncthreads();
-  };
-  for (int t = t0; t < nt; t += 2) {
-    tile(std::integral_constant<int, 1>{}, t);
-    if (t + 1 < nt) tile(std::integral_constant<int, 0>{}, t + 1);
-  }
-  if (a.bias_part && D == 64) {
-    float vq[32];
-#pragma unroll
-    for (int d = 0; d < NDB; ++d)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) vq[16 * d + i] = qvalid ? (float)(bf16)(dq[d][i] * a.scale) : 0.f;
-    const float sq = colsum32(vq, r);
-    a.bias_part[((size_t)b * gridDim.x * 4 + (qblk >> 5) + w) * (3 * a.H * D) + h * D + colsum_col(r, hh)] = sq;
-  }
-  store_rows16<NDB>(a.dq + (size_t)(b * S + q) * a.ld + h * D, dq, a.scale, hh, qvalid);
+  constexpr bool DOC = false;
+#include "attention_bwd_dq_body.h"
+}
+template <int D, int OCC, int BN, int RING>
+__global__ void __launch_bounds__(256, OCC) attn_bwd_dq_doc_kernel(BwdArgs a) {
+  constexpr bool PK = false, RANGE = false, DOC = true;
+#include "attention_bwd_dq_body.h"
 }
 
 #if DTD_ATTN_FUSED_BWD   // experimental builds only (DTD_BUILD_EXPERIMENTAL=1, ops/build.py): the
@@ -1982,10 +1397,14 @@ static bool offsets_fit(int S, int ld, int ldo) {
 
 // kv_range: nullptr, or device int32 [B][2] = (lo, hi) key range per sequence (key-padding mask);
 // the ranged call always takes attn_fwd_kernel's RANGE form (no pipe / packed-fp32 variants).
+// doc: nullptr, or the device int32 [B][S][2] document spans followed by the [B][ceil(S/128)][2]
+// block bounds of a packed batch (FwdArgs): attn_fwd_doc_kernel.
 static int attn_fwd_launch(const void* q, const void* k, const void* v, void* o, float* lse, const float* slopes,
                            uint32_t* masks, int B, int S, int H, int D, int ld, int ldo, int causal, float scale,
-                           float p, const uint64_t* rng, uint32_t sid, const int* kv_range, hipStream_t s) {
+                           float p, const uint64_t* rng, uint32_t sid, const int* kv_range, const int* doc,
+                           hipStream_t s) {
   if (B * S * H == 0) return 0;
+  if (kv_range && doc) return (int)hipErrorInvalidValue;
   if (!offsets_fit(S, ld, ldo)) return (int)hipErrorInvalidValue;
   const int W = (S + 31) / 32;
   uint32_t* mA = nullptr;
@@ -2004,9 +1423,13 @@ static int attn_fwd_launch(const void* q, const void* k, const void* v, void* o,
   const float thr = thr_env ? (float)atof(thr_env) : kRescaleThr;
   const uint32_t* mBk = mA ? mA + (size_t)B * H * (32 * W) * W : nullptr;
   FwdArgs a{(const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, lse, slopes, mA, mBk, B, S, H, ld, ldo, causal, W,
-            scale, p, thr, kv_range};
+            scale, p, thr, doc ? doc : kv_range};
   dim3 grid((S + 127) / 128, B * H);
-  if (kv_range) {
+  if (doc) {
+    if (D == 64) hipLaunchKernelGGL((attn_fwd_doc_kernel<64, 3, 64, 1>), grid, dim3(256), 0, s, a);
+    else if (D == 128) hipLaunchKernelGGL((attn_fwd_doc_kernel<128, 1, 64, 2>), grid, dim3(256), 0, s, a);
+    else return (int)hipErrorInvalidValue;
+  } else if (kv_range) {
     if (D == 64) hipLaunchKernelGGL((attn_fwd_kernel<64, 3, 64, 1, false, true>), grid, dim3(256), 0, s, a);
     else if (D == 128) hipLaunchKernelGGL((attn_fwd_kernel<128, 1, 64, 2, false, true>), grid, dim3(256), 0, s, a);
     else return (int)hipErrorInvalidValue;
@@ -2030,7 +1453,8 @@ static int attn_fwd_launch(const void* q, const void* k, const void* v, void* o,
 DTD_EXPORT int dtd_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const float* slopes,
                             uint32_t* masks, int B, int S, int H, int D, int ld, int ldo, int causal, float scale,
                             float p, const uint64_t* rng, uint32_t sid, hipStream_t s) {
-  return attn_fwd_launch(q, k, v, o, lse, slopes, masks, B, S, H, D, ld, ldo, causal, scale, p, rng, sid, nullptr, s);
+  return attn_fwd_launch(q, k, v, o, lse, slopes, masks, B, S, H, D, ld, ldo, causal, scale, p, rng, sid, nullptr,
+                         nullptr, s);
 }
 
 // dtd_attn_fwd with a per-sequence key range (kv_range: device int32 [B][2], required)
@@ -2039,7 +1463,18 @@ DTD_EXPORT int dtd_attn_fwd_range(const void* q, const void* k, const void* v, v
                                   int causal, float scale, float p, const uint64_t* rng, uint32_t sid,
                                   const int* kv_range, hipStream_t s) {
   if (!kv_range) return (int)hipErrorInvalidValue;
-  return attn_fwd_launch(q, k, v, o, lse, slopes, masks, B, S, H, D, ld, ldo, causal, scale, p, rng, sid, kv_range, s);
+  return attn_fwd_launch(q, k, v, o, lse, slopes, masks, B, S, H, D, ld, ldo, causal, scale, p, rng, sid, kv_range,
+                         nullptr, s);
+}
+
+// dtd_attn_fwd for a packed batch: doc = device int32 [B][S][2] document span of every position,
+// followed by the [B][ceil(S/128)][2] bounds per 128-position block (required)
+DTD_EXPORT int dtd_attn_fwd_doc(const void* q, const void* k, const void* v, void* o, float* lse, const float* slopes,
+                                uint32_t* masks, int B, int S, int H, int D, int ld, int ldo, int causal, float scale,
+                                float p, const uint64_t* rng, uint32_t sid, const int* doc, hipStream_t s) {
+  if (!doc) return (int)hipErrorInvalidValue;
+  return attn_fwd_launch(q, k, v, o, lse, slopes, masks, B, S, H, D, ld, ldo, causal, scale, p, rng, sid, nullptr,
+                         doc, s);
 }
 
 // 0 = the dQ + dK/dV pair, 1 = fused where it applies, 2 = fused, 4-wave form; returns the previous
@@ -2088,6 +1523,16 @@ static void launch_dkdv_range(dim3 grid, hipStream_t s, const BwdArgs& a) {
   else hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, OCC, BM, false, false, true, true>), grid, dim3(256), 0, s, a);
 }
 
+// With document spans: attn_bwd_dkdv_doc_kernel, the masked form as well.
+template <int D, int OCC, int BM>
+static void launch_dkdv_doc(dim3 grid, hipStream_t s, const BwdArgs& a) {
+  const bool drop = a.maskB != nullptr, alibi = a.slopes != nullptr;
+  if (drop && alibi) hipLaunchKernelGGL((attn_bwd_dkdv_doc_kernel<D, OCC, BM, true, true>), grid, dim3(256), 0, s, a);
+  else if (drop) hipLaunchKernelGGL((attn_bwd_dkdv_doc_kernel<D, OCC, BM, true, false>), grid, dim3(256), 0, s, a);
+  else if (alibi) hipLaunchKernelGGL((attn_bwd_dkdv_doc_kernel<D, OCC, BM, false, true>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((attn_bwd_dkdv_doc_kernel<D, OCC, BM, false, false>), grid, dim3(256), 0, s, a);
+}
+
 // Which kernels of the split backward run (bit 0: dQ, bit 1: dK/dV): a timing hook for
 // scripts/bench_attn.py, which prices the two kernels separately.  Anything but 3 leaves part of
 // the gradient unwritten (and dK/dV alone reads a delta the skipped dQ kernel did not write).
@@ -2100,12 +1545,13 @@ DTD_EXPORT int dtd_attn_set_bwd_kernels(int mask) {
 
 // dq/dk/dv: bf16 views with row stride ld into dqkv.  `delta` is [B,H,S] fp32 scratch.
 // kv_range: nullptr, or device int32 [B][2] key range per sequence; the ranged call always runs
-// the split dQ + dK/dV pair in its default tile forms.
+// the split dQ + dK/dV pair in its default tile forms.  doc (see attn_fwd_launch): likewise.
 static int attn_bwd_launch(const void* q, const void* k, const void* v, const void* o, const void* dout,
                            const float* lse, float* delta, const uint32_t* masks, void* dq, void* dk, void* dv,
                            const float* slopes, int B, int S, int H, int D, int ld, int ldo, int causal, float scale,
-                           float p, float* bias_part, const int* kv_range, hipStream_t s) {
+                           float p, float* bias_part, const int* kv_range, const int* doc, hipStream_t s) {
   if (B * S * H == 0) return 0;
+  if (kv_range && doc) return (int)hipErrorInvalidValue;
   if (D != 64 && D != 128) return (int)hipErrorInvalidValue;
   if (!offsets_fit(S, ld, ldo)) return (int)hipErrorInvalidValue;
   const int W = (S + 31) / 32;
@@ -2115,8 +1561,18 @@ static int attn_bwd_launch(const void* q, const void* k, const void* v, const vo
   dim3 grid((S + 127) / 128, B * H);
   BwdArgs a{(const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)dout, lse, delta, (const bf16*)o,
             (bf16*)dq, (bf16*)dk, (bf16*)dv, slopes, mA, mB, B, S, H, ld, ldo, causal, W, scale, p,
-            D == 64 ? bias_part : nullptr, kv_range};
+            D == 64 ? bias_part : nullptr, doc ? doc : kv_range};
   const bool run_dq = g_bwd_kernels & 1, run_dkdv = g_bwd_kernels & 2;
+  if (doc) {
+    if (D == 64) {
+      if (run_dq) hipLaunchKernelGGL((attn_bwd_dq_doc_kernel<64, 3, 64, 1>), grid, dim3(256), 0, s, a);
+      if (run_dkdv) launch_dkdv_doc<64, 2, 128>(grid, s, a);
+    } else {
+      if (run_dq) hipLaunchKernelGGL((attn_bwd_dq_doc_kernel<128, 1, 64, 2>), grid, dim3(256), 0, s, a);
+      if (run_dkdv) launch_dkdv_doc<128, 1, 64>(grid, s, a);
+    }
+    DTD_LAUNCH_CHECK();
+  }
   if (kv_range) {
     if (D == 64) {
       if (run_dq) hipLaunchKernelGGL((attn_bwd_dq_kernel<64, 3, 64, 1, false, true>), grid, dim3(256), 0, s, a);
@@ -2180,7 +1636,7 @@ DTD_EXPORT int dtd_attn_bwd(const void* q, const void* k, const void* v, const v
                             const float* slopes, int B, int S, int H, int D, int ld, int ldo, int causal, float scale,
                             float p, float* bias_part, hipStream_t s) {
   return attn_bwd_launch(q, k, v, o, dout, lse, delta, masks, dq, dk, dv, slopes, B, S, H, D, ld, ldo, causal, scale,
-                         p, bias_part, nullptr, s);
+                         p, bias_part, nullptr, nullptr, s);
 }
 
 // dtd_attn_bwd with a per-sequence key range (kv_range: device int32 [B][2], required)
@@ -2190,5 +1646,15 @@ DTD_EXPORT int dtd_attn_bwd_range(const void* q, const void* k, const void* v, c
                                   float scale, float p, float* bias_part, const int* kv_range, hipStream_t s) {
   if (!kv_range) return (int)hipErrorInvalidValue;
   return attn_bwd_launch(q, k, v, o, dout, lse, delta, masks, dq, dk, dv, slopes, B, S, H, D, ld, ldo, causal, scale,
-                         p, bias_part, kv_range, s);
+                         p, bias_part, kv_range, nullptr, s);
+}
+
+// dtd_attn_bwd for a packed batch (doc as in dtd_attn_fwd_doc, required)
+DTD_EXPORT int dtd_attn_bwd_doc(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                                const float* lse, float* delta, const uint32_t* masks, void* dq, void* dk, void* dv,
+                                const float* slopes, int B, int S, int H, int D, int ld, int ldo, int causal,
+                                float scale, float p, float* bias_part, const int* doc, hipStream_t s) {
+  if (!doc) return (int)hipErrorInvalidValue;
+  return attn_bwd_launch(q, k, v, o, dout, lse, delta, masks, dq, dk, dv, slopes, B, S, H, D, ld, ldo, causal, scale,
+                         p, bias_part, nullptr, doc, s);
 }

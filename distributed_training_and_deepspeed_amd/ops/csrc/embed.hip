@@ -20,16 +20,21 @@ struct GatherArgs {
   const int64_t* ids; const int64_t* type_ids;
   const void* word; const void* pos; const void* type;
   void* out; int rows, h, seq, pos_offset;
+  // PID kernels (sequence packing): the position of each row, read instead of row % seq, and the
+  // number of rows of the position table (the index is clamped into it)
+  const int64_t* pos_ids; int pos_rows;
 };
 
 // One wave per output row (4 rows per block), VEC-wide (16-byte for bf16) loads of the word,
 // position and token-type rows.
-template <typename T, int VEC>
+// PID: the position comes from a.pos_ids (a packed row's positions restart at every document).
+template <typename T, int VEC, bool PID = false>
 __global__ void __launch_bounds__(256) embed_fwd_kernel(GatherArgs a) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= a.rows) return;
   const int64_t id = a.ids[row];
-  const int pidx = (row % a.seq) + a.pos_offset;
+  int pidx = (row % a.seq) + a.pos_offset;
+  if constexpr (PID) pidx = (int)min(max(a.pos_ids[row] + a.pos_offset, (int64_t)0), (int64_t)a.pos_rows - 1);
   const int64_t tid = a.type_ids ? a.type_ids[row] : 0;
   const T* w = (const T*)a.word + (size_t)id * a.h;
   const T* p = a.pos ? (const T*)a.pos + (size_t)pidx * a.h : nullptr;
@@ -306,7 +311,7 @@ DTD_EXPORT int dtd_embed_fwd(int dtype, const int64_t* ids, const int64_t* type_
                              const void* type, void* out, int rows, int h, int seq, int pos_offset, hipStream_t s) {
   if (rows <= 0) return 0;
   if (h % 2) return (int)hipErrorInvalidValue;
-  GatherArgs a{ids, type_ids, word, pos, type, out, rows, h, seq, pos_offset};
+  GatherArgs a{ids, type_ids, word, pos, type, out, rows, h, seq, pos_offset, nullptr, 0};
   const dim3 grid((rows + 3) / 4);
   if (dtype == kBF16) {
     if (h % 8 == 0) hipLaunchKernelGGL((embed_fwd_kernel<bf16, 8>), grid, dim3(256), 0, s, a);
@@ -314,6 +319,25 @@ DTD_EXPORT int dtd_embed_fwd(int dtype, const int64_t* ids, const int64_t* type_
   } else {
     if (h % 4 == 0) hipLaunchKernelGGL((embed_fwd_kernel<float, 4>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((embed_fwd_kernel<float, 2>), grid, dim3(256), 0, s, a);
+  }
+  DTD_LAUNCH_CHECK();
+}
+
+// dtd_embed_fwd with the position of every row read from pos_ids[rows] (int64, required, as is the
+// position table): row r takes table row pos_ids[r] + pos_offset, clamped into [0, pos_rows).
+DTD_EXPORT int dtd_embed_fwd_pos(int dtype, const int64_t* ids, const int64_t* type_ids, const int64_t* pos_ids,
+                                 const void* word, const void* pos, const void* type, void* out, int rows, int h,
+                                 int pos_offset, int pos_rows, hipStream_t s) {
+  if (rows <= 0) return 0;
+  if (h % 2 || !pos_ids || !pos || pos_rows <= 0) return (int)hipErrorInvalidValue;
+  GatherArgs a{ids, type_ids, word, pos, type, out, rows, h, 1, pos_offset, pos_ids, pos_rows};
+  const dim3 grid((rows + 3) / 4);
+  if (dtype == kBF16) {
+    if (h % 8 == 0) hipLaunchKernelGGL((embed_fwd_kernel<bf16, 8, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((embed_fwd_kernel<bf16, 2, true>), grid, dim3(256), 0, s, a);
+  } else {
+    if (h % 4 == 0) hipLaunchKernelGGL((embed_fwd_kernel<float, 4, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((embed_fwd_kernel<float, 2, true>), grid, dim3(256), 0, s, a);
   }
   DTD_LAUNCH_CHECK();
 }

@@ -499,14 +499,23 @@ class CrossEntropyLoss(torch.nn.Module):
 # embeddings
 # --------------------------------------------------------------------------------------
 def embed_fwd(ids: torch.Tensor, word: torch.Tensor, pos: torch.Tensor | None, type_: torch.Tensor | None,
-              seq: int, pos_offset: int = 0, type_ids: torch.Tensor | None = None) -> torch.Tensor:
+              seq: int, pos_offset: int = 0, type_ids: torch.Tensor | None = None,
+              position_ids: torch.Tensor | None = None) -> torch.Tensor:
+    """``position_ids``: optional integer positions, one per id (sequence packing: they restart at
+    every document); row r then takes position-table row ``position_ids[r] + pos_offset`` instead
+    of ``r % seq + pos_offset``.  The kernel clamps that row index into the table."""
     rows = ids.numel()
     h = word.shape[1]
+    if position_ids is not None and (pos is None or position_ids.numel() != rows):
+        raise ValueError("position_ids needs a position table and one position per id")
     if not _on_gpu(word):
         flat = ids.reshape(-1)
         out = word[flat].float()
         if pos is not None:
-            pidx = torch.arange(rows, device=ids.device) % seq + pos_offset
+            if position_ids is not None:
+                pidx = (position_ids.reshape(-1).to(torch.int64) + pos_offset).clamp(0, pos.shape[0] - 1)
+            else:
+                pidx = torch.arange(rows, device=ids.device) % seq + pos_offset
             out = out + pos[pidx].float()
         if type_ is not None:
             tid = type_ids.reshape(-1) if type_ids is not None else torch.zeros_like(flat)
@@ -515,19 +524,28 @@ def embed_fwd(ids: torch.Tensor, word: torch.Tensor, pos: torch.Tensor | None, t
     out = torch.empty((rows, h), dtype=word.dtype, device=word.device)
     ids_c = ids.reshape(-1).contiguous().to(torch.int64)
     tids = type_ids.reshape(-1).contiguous().to(torch.int64) if type_ids is not None else None
+    if position_ids is not None:
+        if not _lib.has("dtd_embed_fwd_pos"):
+            raise _lib.KernelError("the kernel library has no position-id embedding entry point (stale build)")
+        pids = position_ids.reshape(-1).contiguous().to(device=word.device, dtype=torch.int64)
+        _lib.call("dtd_embed_fwd_pos", _lib.dt(word), ids_c.data_ptr(), _lib.ptr(tids), pids.data_ptr(),
+                  word.data_ptr(), pos.data_ptr(), _lib.ptr(type_), out.data_ptr(), rows, h, pos_offset,
+                  pos.shape[0], _lib.stream())
+        return out
     _lib.call("dtd_embed_fwd", _lib.dt(word), ids_c.data_ptr(), _lib.ptr(tids), word.data_ptr(), _lib.ptr(pos),
               _lib.ptr(type_), out.data_ptr(), rows, h, seq, pos_offset, _lib.stream())
     return out
 
 
 def embed_ln_fwd(ids, word, pos, type_, seq: int, pos_offset: int, gamma, beta, eps: float, p: float,
-                 rng: RngState, sid: int, type_ids=None):
+                 rng: RngState, sid: int, type_ids=None, position_ids=None):
     """Embedding gather-sum + LayerNorm + dropout in one kernel: returns (out, z, mean, rstd), the
     same values as ``embed_fwd`` -> ``ln_fwd(None, z, ...)`` -> ``dropout`` (z = the LN input the
     backward needs), or None when the fused kernel does not cover the case (CPU, fp32, h other
-    than 768 / 1024): the caller then runs the three passes."""
+    than 768 / 1024, or ``position_ids`` given -- the fused kernel derives positions from the row
+    index only): the caller then runs the three passes."""
     h = word.shape[1]
-    if (not _on_gpu(word) or word.dtype != torch.bfloat16 or h not in (768, 1024) or gamma is None
+    if (position_ids is not None or not _on_gpu(word) or word.dtype != torch.bfloat16 or h not in (768, 1024) or gamma is None
             or not _lib.has("dtd_embed_ln_fwd")
             or any(t is not None and (t.dtype != torch.bfloat16 or not t.is_contiguous())
                    for t in (word, pos, type_, gamma, beta))):
@@ -587,8 +605,15 @@ def embed_word_bwd(ids: torch.Tensor, dz: torch.Tensor, grad: torch.Tensor, acc:
               padding_idx, _lib.stream())
 
 
-def embed_pos_bwd(dz: torch.Tensor, grad: torch.Tensor, batch: int, seq: int, pos_offset: int, acc: bool):
+def embed_pos_bwd(dz: torch.Tensor, grad: torch.Tensor, batch: int, seq: int, pos_offset: int, acc: bool,
+                  position_ids: torch.Tensor | None = None):
+    """``position_ids`` (sequence packing): the positions repeat inside a row, so the gradient is a
+    segment sum with duplicates -- the sorted, atomic-free path of the word table, keyed by the
+    position-table row (clamped like the forward's)."""
     h = grad.shape[1]
+    if position_ids is not None:
+        rows = (position_ids.reshape(-1).to(torch.int64) + pos_offset).clamp(0, grad.shape[0] - 1)
+        return embed_word_bwd(rows, dz, grad, acc)
     if not _on_gpu(grad):
         s = dz.reshape(batch, seq, h).float().sum(0)
         if not acc:

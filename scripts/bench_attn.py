@@ -5,14 +5,19 @@ variants (DTD_ATTN_OCC="fwd,dkdv,dq" waves/SIMD).  Prints one JSON line per vari
 fwd_us: forward kernel with the dropout keep bits generated ahead (as in the model, where the
 mask kernel runs on a side stream under the forward GEMMs); mask_us: the mask generator alone;
 bwd_us: dK/dV + dQ, or the one-kernel fused backward for a variant named "fused" (or "fused:<occ>").
-Env: B, H, P, CAUSAL=1 (model FLOPs are quoted for the full square).
+Env: B, H, P, CAUSAL=1 (model FLOPs are quoted for the full square), ALIBI=1 (ALiBi slopes, with
+``--valid-frac`` / ``--docs``).
 
 ``--valid-frac F [F ...]``: the key-range (key-padding mask) kernels instead -- every row gets the
 right-padded range (0, round(F * S)).  One JSON line per fraction with the forward, dQ, dK/dV and
 whole-backward times (dq_us / dkdv_us: each kernel alone, ops.attention.set_bwd_kernels), plus a
 line ``"valid_frac": null`` for the call without a range.  The configurations are timed
 interleaved, ``--rounds`` times over; each figure is the median of its rounds (the spread is in
-``*_minmax``).  ``--out FILE`` appends the lines to a jsonl file, ``--tag`` labels them."""
+``*_minmax``).  ``--out FILE`` appends the lines to a jsonl file, ``--tag`` labels them.
+
+``--docs N [N ...]``: the document-mask (sequence packing) kernels -- every row holds N equal
+documents (S // N tokens each, the last takes the remainder).  Same records, with ``"docs": N``;
+interleaved with the call without a range like ``--valid-frac`` (both flags may be given)."""
 import argparse
 import json
 import os
@@ -40,26 +45,38 @@ def timeit(fn, iters=20):
     return e0.elapsed_time(e1) / iters * 1e3
 
 
-def ranged(args, B, S, H, D, p, causal, qkv, dctx, rng):
-    """Forward / dQ / dK/dV times per valid fraction (None = no range), interleaved over rounds.
+def equal_docs(B, S, n):
+    """DocRange of B rows of n equal documents."""
+    seg = torch.clamp(torch.arange(S, device="cuda") // max(S // n, 1), max=n - 1) + 1
+    return A.doc_range_from_segment_ids(seg.view(1, S).expand(B, S).contiguous())
+
+
+def ranged(args, B, S, H, D, p, causal, qkv, dctx, rng, slopes=None):
+    """Forward / dQ / dK/dV times per valid fraction / document count (None = no range),
+    interleaved over rounds.
     With a kernel library from before the key ranges (DTD_KERNELS_SO=<older build>, the yardstick
     of an A/B) only the call without a range is timed, forward and whole backward."""
     has_range = _lib.has("dtd_attn_fwd_range") and _lib.has("dtd_attn_set_bwd_kernels")
-    configs = [None] + (list(args.valid_frac) if has_range else [])
+    configs = [None] + ([("valid_frac", f) for f in args.valid_frac or []] if has_range else []) \
+        + [("docs", n) for n in args.docs or []]
     pend = A.attn_masks_async(B, S, H, D, p, rng, 3, qkv.device) if p > 0 else None
     torch.cuda.synchronize()
     state = {}
     for f in configs:
-        kr = None if f is None else torch.tensor([[0, int(round(f * S))]] * B, dtype=torch.int32, device="cuda")
-        ctx, lse, mk = A.attn_fwd(qkv, B, S, H, D, causal, None, p, rng, 3, masks=pend, key_range=kr)
+        kr = {}
+        if f is not None and f[0] == "valid_frac":
+            kr = {"key_range": torch.tensor([[0, int(round(f[1] * S))]] * B, dtype=torch.int32, device="cuda")}
+        elif f is not None:
+            kr = {"doc_range": equal_docs(B, S, f[1])}
+        ctx, lse, mk = A.attn_fwd(qkv, B, S, H, D, causal, slopes, p, rng, 3, masks=pend, **kr)
         state[f] = (kr, ctx, lse, mk)
     times = {f: {"fwd_us": [], "dq_us": [], "dkdv_us": [], "bwd_us": []} for f in configs}
     for _ in range(args.rounds):
         for f in configs:
             kr, ctx, lse, mk = state[f]
             t = times[f]
-            t["fwd_us"].append(timeit(lambda: A.attn_fwd(qkv, B, S, H, D, causal, None, p, rng, 3, masks=pend, key_range=kr)))
-            bwd = lambda: A.attn_bwd(dctx, qkv, ctx, lse, B, S, H, D, causal, None, p, rng, 3, mk, key_range=kr)  # noqa: E731
+            t["fwd_us"].append(timeit(lambda: A.attn_fwd(qkv, B, S, H, D, causal, slopes, p, rng, 3, masks=pend, **kr)))
+            bwd = lambda: A.attn_bwd(dctx, qkv, ctx, lse, B, S, H, D, causal, slopes, p, rng, 3, mk, **kr)  # noqa: E731
             t["bwd_us"].append(timeit(bwd))
             if not has_range:
                 continue
@@ -71,8 +88,11 @@ def ranged(args, B, S, H, D, p, causal, qkv, dctx, rng):
             finally:
                 A.set_bwd_kernels(True, True)
     for f in configs:
-        rec = {"tag": args.tag, "valid_frac": f, "B": B, "S": S, "H": H, "D": D, "causal": causal, "p": p,
-               "rounds": args.rounds}
+        rec = {"tag": args.tag, "valid_frac": f[1] if f and f[0] == "valid_frac" else None, "B": B, "S": S, "H": H,
+               "D": D, "causal": causal, "p": p, "rounds": args.rounds}
+        if args.docs:
+            rec["docs"] = f[1] if f and f[0] == "docs" else None
+            rec["alibi"] = slopes is not None
         for k, v in times[f].items():
             if not v:
                 continue
@@ -90,6 +110,8 @@ def main():
     ap.add_argument("occ", nargs="*", help='occupancy variants "fwd,dkdv,dq", "fused" or "fused:<occ>"')
     ap.add_argument("--valid-frac", type=float, nargs="+", default=None,
                     help="time the key-range kernels at these valid fractions of S (right-padded rows)")
+    ap.add_argument("--docs", type=int, nargs="+", default=None,
+                    help="time the document-mask kernels with this many equal documents per row")
     ap.add_argument("--rounds", type=int, default=5, help="--valid-frac: interleaved rounds per configuration")
     ap.add_argument("--out", default="", help="--valid-frac: append the JSON lines to this file")
     ap.add_argument("--tag", default="", help="--valid-frac: label of the records")
@@ -105,8 +127,9 @@ def main():
     for _ in range(50):
         A.attn_fwd(qkv, B, S, H, D, causal, None, p, rng, 3)
     torch.cuda.synchronize()
-    if args.valid_frac is not None:
-        ranged(args, B, S, H, D, p, causal, qkv, dctx, rng)
+    if args.valid_frac is not None or args.docs is not None:
+        slopes = A.alibi_slopes(H) if os.environ.get("ALIBI", "0") == "1" else None
+        ranged(args, B, S, H, D, p, causal, qkv, dctx, rng, slopes)
         return
     for occ in args.occ or ["1,1,1", "2,2,2", "3,2,2", "3,2,3"]:
         form = occ.split(":", 1)[0] if occ.startswith("fused") else "split"

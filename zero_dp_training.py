@@ -96,17 +96,22 @@ def train(model_name, batch_size, training_steps, stage, opts):
 
     # --pad-fraction: that share of the rows is right-padded to a random length; --attention-mask:
     # the rows' 0/1 mask goes to the model, whose attention then leaves the pad keys out (default
-    # off: pads attended to, as in the reference)
+    # off: pads attended to, as in the reference).  --pack-docs N: every row holds 1 to N documents;
+    # the rows' segment_ids go to the model and no label crosses a document boundary
     dataset = load_synthetic(cfg, batch_size * training_steps, seq_len=opts.seq_len, mlm=False, seed=0,
-                             pad_fraction=opts.pad_fraction, return_attention_mask=opts.attention_mask)
+                             pad_fraction=opts.pad_fraction, return_attention_mask=opts.attention_mask,
+                             max_docs=opts.pack_docs)
     sampler = DistributedSampler(dataset, num_replicas=world_size, rank=int(os.getenv("RANK", rank)))
-    keys = ("input_ids", "labels") + (("attention_mask",) if opts.attention_mask else ())
+    keys = ("input_ids", "labels") + (("attention_mask",) if opts.attention_mask else ()) \
+        + (("segment_ids",) if opts.pack_docs else ())
     loader = DeviceBatchLoader(dataset, batch_size=batch_size, sampler=sampler, device=device, keys=keys)
     model_engine.train()
     dist_log.comms_logger.reset()  # only the training loop's collectives are summed below
 
-    def train_step(input_ids, labels, attention_mask=None):
-        if attention_mask is None:
+    def train_step(input_ids, labels, attention_mask=None, segment_ids=None):
+        if segment_ids is not None:
+            outputs = model_engine(input_ids, labels=labels, segment_ids=segment_ids)
+        elif attention_mask is None:
             outputs = model_engine(input_ids, labels=labels)
         else:
             outputs = model_engine(input_ids, labels=labels, attention_mask=attention_mask)
@@ -141,7 +146,7 @@ def train(model_name, batch_size, training_steps, stage, opts):
     n = 0  # timed steps (graph warm-up steps trained before the clock started)
     for batch in batches:
         if graphed is not None and batch["input_ids"].shape == graphed.static["input_ids"].shape:
-            loss = graphed(**batch)   # (with --attention-mask: the mask is a third static input)
+            loss = graphed(**batch)   # (--attention-mask / --pack-docs: the mask / segment ids are a third static input)
         else:
             loss = train_step(**batch)
         n += 1
@@ -160,7 +165,9 @@ def train(model_name, batch_size, training_steps, stage, opts):
     if rank == 0:
         print(f"\nTotal Communication Latency: {total_comms_latency:.2f} ms")
         tokens = n * batch_size * opts.seq_len * world_size
-        print(json.dumps({"tokens_per_s": round(tokens / max(elapsed, 1e-9), 1), "stage": stage,
+        labelled = float((dataset.labels != -100).float().mean())   # share of positions with a label
+        print(json.dumps({"tokens_per_s": round(tokens / max(elapsed, 1e-9), 1),
+                          "labelled_tokens_per_s": round(labelled * tokens / max(elapsed, 1e-9), 1), "stage": stage,
                           "partition_numel": model_engine.partition_numel(),
                           "final_loss": round(float(loss.detach()), 4), "hip_graph": graphed is not None}))
     comm.destroy()
@@ -188,11 +195,16 @@ if __name__ == "__main__":
                         help="pass the rows' attention_mask to the model: pad keys are not attended to")
     parser.add_argument("--pad-fraction", type=float, default=0.0,
                         help="share of the synthetic rows right-padded to a random length")
+    parser.add_argument("--pack-docs", type=int, default=0, metavar="N",
+                        help="sequence packing: cut every synthetic row into 1 to N documents and pass the rows' "
+                             "segment_ids to the model (excludes --attention-mask)")
     parser.add_argument("--graph", nargs="?", const="on", default="auto", choices=["auto", "on", "off"],
                         help="capture the whole training step in a hipGraph and replay it, at any ZeRO stage "
                              "(auto: on for one GPU, where batch-1 steps are host-launch bound)")
     parser.add_argument("--quiet", action="store_true")
     args, extra_args = parser.parse_known_args()
+    if args.pack_docs and args.attention_mask:
+        parser.error("--pack-docs and --attention-mask are mutually exclusive (segment id 0 marks the padding)")
     if args.num_gpus and "WORLD_SIZE" not in os.environ:
         launch(_spawned, args=(args,), nprocs=args.num_gpus)
     else:
