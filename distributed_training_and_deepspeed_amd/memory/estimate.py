@@ -179,3 +179,18 @@ def max_hidden_for_capacity(capacity: float = MI355X_HBM_BYTES, layers: int = 1,
         else:
             hi = mid - 1
     return 128 * lo
+
+
+def lm_head_transient_bytes(tokens: int, vocab: int, fused: bool = False, chunks: int = 8, dtype_bytes: int = 2) -> int:
+    """Peak [tokens, vocab]-shaped transient memory of the causal-LM head's loss on one device.
+
+    ``fused=False`` (``Runtime.head_loss = "logits"``): the logits, kept from the forward to the
+    backward, plus dlogits -- 2 x tokens x vocab elements (bloom-560m, 512 tokens: 2 x 257 MB).
+    ``fused=True``: the one reused chunk of dlogits of the chunked backward, the largest block of
+    ``ops.functional.head_xent_plan`` (the forward keeps no such tensor).  The fp32 input-gradient
+    accumulator (tokens x hidden x 4) and the forward's per-range partials are not vocabulary-sized
+    and are left out.  Not part of the ``project_*`` totals above."""
+    if not fused:
+        return 2 * tokens * vocab * dtype_bytes
+    from ..ops.functional import head_xent_plan
+    return max((r1 - r0) * (v1 - v0) for r0, r1, v0, v1 in head_xent_plan(tokens, vocab, 0, chunks)) * dtype_bytes

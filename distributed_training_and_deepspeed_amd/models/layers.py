@@ -11,7 +11,8 @@
   identical to the dense head (unlabelled rows contribute exactly zero), it just skips the
   logits that CrossEntropyLoss(ignore_index=-100) would discard.
 * ``LMHead``: tied causal-LM head with the shifted-label cross entropy of HF *ForCausalLM,
-  computed only on the S-1 positions that have a next-token label.
+  computed only on the S-1 positions that have a next-token label.  ``Runtime.head_loss =
+  "fused"`` computes it without the [B*S, V] logits and dlogits tensors (ops/csrc/head_xent.hip).
 """
 from __future__ import annotations
 
@@ -23,7 +24,7 @@ from torch import nn
 
 from ..ops import functional as Fx
 from ..ops import gemm as G
-from ..ops.grad import emit_wgrad, grad_done, grad_dst, note_use
+from ..ops.grad import emit_wgrad, gemm_into, grad_done, grad_dst, note_use, wgrad_rows_into
 
 from .config import TransformerConfig
 from .transformer import Runtime, init_linear_, ref_dropout
@@ -379,6 +380,64 @@ class _LMHeadFn(torch.autograd.Function):
         return G.head_dgrad(dlogits, w), None, None, None
 
 
+def _dx_splits(rows: int, width: int) -> int:
+    """K-split of one chunk's input-gradient product d [rows, width] @ w [width, h].  Each chunk is a
+    launch of its own, so up to 1024 rows (an output of a few dozen tiles) it takes the 16 ranges of
+    ops/gemm.py::head_splits whatever the number of chunks, as long as a range keeps 1024 columns:
+    bloom-560m's head at 512 rows, forward + backward 2033 -> 1820 us.  At 4096 rows the output
+    fills the chip; 8 ranges there gained 4 % at 250880 x 1024 and lost 14 % at 50272 x 768
+    (profiles/head_xent.jsonl holds the shipped form), so those take the plain product."""
+    s = 16 if rows <= 1024 else 0
+    while s > 1 and (width % s or width // s < 1024):
+        s //= 2
+    return s if s > 1 else 0
+
+
+class _LMHeadFusedFn(torch.autograd.Function):
+    """The head's loss without the logits (``Runtime.head_loss = "fused"``): the forward keeps
+    x, labels, lse and stats; the backward walks ``Fx.head_xent_plan`` with one reused chunk of
+    dlogits -- recompute the chunk, its rows of the weight gradient, its share of the input gradient
+    (fp32 accumulator, rounded once)."""
+
+    @staticmethod
+    def forward(ctx, x, labels, head, w):
+        loss, lse, stats = Fx.head_xent_fwd(x, w, labels)
+        ctx.save_for_backward(x, labels, lse, stats)
+        ctx.head = head
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        x, labels, lse, stats = ctx.saved_tensors
+        head = ctx.head
+        w = head.weight
+        T, h = x.shape
+        V = w.shape[0]
+        plan = Fx.head_xent_plan(T, V, h, max(1, int(head.rt.head_chunks)))
+        rows = max(r1 - r0 for r0, r1, _, _ in plan)
+        width = max(v1 - v0 for _, _, v0, v1 in plan)
+        buf = torch.empty((rows, width), dtype=x.dtype, device=x.device)   # the one chunk of dlogits
+        dx32 = torch.empty((T, h), dtype=torch.float32, device=x.device)
+        dst, acc = grad_dst(w)   # the tied embedding: one slot, one accumulate flag for every block
+        for r0, r1, v0, v1 in plan:
+            xr = x[r0:r1]
+            d = Fx.head_xent_dlogits(xr, w, labels[r0:r1], lse[r0:r1], stats, gloss, v0, v1, out=buf)
+            wgrad_rows_into(dst, acc or r0 > 0, v0, v1, d, xr)
+            wv = w[v0:v1]
+            s = _dx_splits(r1 - r0, v1 - v0) if d.is_cuda and d.dtype != torch.float32 else 0
+            if s:
+                part = torch.bmm(d.view(r1 - r0, s, (v1 - v0) // s).transpose(0, 1),
+                                 wv.view(s, (v1 - v0) // s, h), out_dtype=torch.float32)
+                if v0 == 0:
+                    torch.sum(part, 0, out=dx32[r0:r1])
+                else:
+                    dx32[r0:r1] += part.sum(0)
+            else:
+                gemm_into(dx32[r0:r1], d, wv, v0 > 0)
+        grad_done(w)
+        return dx32.to(x.dtype), None, None, None
+
+
 class LMHead(nn.Module):
     def __init__(self, cfg: TransformerConfig, rt: Runtime, word_embeddings: nn.Parameter):
         super().__init__()
@@ -406,6 +465,8 @@ class LMHead(nn.Module):
             # runs over the same labelled rows.  bloom-560m b1: 512 instead of 511 rows makes the
             # logits / weight-gradient GEMMs 251 / 376 us vs 292 / 426 (profiles/r6_head_rows.json)
             ls = torch.cat([labels[:, 1:], labels.new_full((B, 1), Fx.IGNORE_INDEX)], 1).reshape(-1)
+            if self.rt.head_loss == "fused":   # no [B*S, V] logits, one chunk of dlogits at a time
+                return _LMHeadFusedFn.apply(x.reshape(-1, h), ls, self, self.weight)
             return _LMHeadFn.apply(x.reshape(-1, h), ls, self, self.weight)
         xs = x[:, :-1].reshape(-1, h)
         ls = labels[:, 1:].reshape(-1)

@@ -63,6 +63,12 @@ class Runtime:
         # memory-efficient post-LN backward for this model: None follows DTD_LN_MEMEFF; loading a
         # state dict whose LayerNorms are ill-conditioned for it sets False (ln_memeff_safe)
         self.ln_memeff: bool | None = None
+        # Causal-LM head loss: "logits" materialises the [T, V] logits (and dlogits in the backward);
+        # "fused" (DTD_HEAD_XENT=1) computes the loss from logit tiles that never leave the kernel and
+        # runs the backward over ``head_chunks`` vocabulary chunks (DTD_HEAD_XENT_CHUNKS) with one
+        # reused chunk of dlogits.  See LMHead.loss.
+        self.head_loss = "fused" if os.environ.get("DTD_HEAD_XENT", "0") == "1" else "logits"
+        self.head_chunks = int(os.environ.get("DTD_HEAD_XENT_CHUNKS", "8"))
 
     def new_sid(self) -> int:
         """Dropout stream id for one call site; deterministic per model structure so two

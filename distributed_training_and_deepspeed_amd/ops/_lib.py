@@ -27,6 +27,7 @@ I = ctypes.c_int
 F = ctypes.c_float
 SZ = ctypes.c_size_t
 U32 = ctypes.c_uint32
+L = ctypes.c_long
 
 _SIGS = {
     # norm.hip
@@ -50,6 +51,12 @@ _SIGS = {
     "dtd_xent_bwd_colsum": (I, [P, P, P, P, P, P, P, I, I, I, P]),
     "dtd_xent_fwd_train": (I, [P, P, P, P, P, P, P, I, I, I, P]),
     "dtd_xent_grad_scale": (I, [P, SZ, P, P]),
+    # head_xent.hip
+    "dtd_head_xent_supported": (I, [I, I, I]),
+    "dtd_head_lse_ranges": (I, [I, I]),
+    "dtd_head_lse": (I, [P, L, P, L, P, P, P, P, P, P, I, I, I, I, P]),
+    "dtd_head_dlogits_max_elems": (L, []),
+    "dtd_head_dlogits": (I, [P, L, P, L, P, P, P, P, P, L, I, I, I, I, I, I, P]),
     # embed.hip
     "dtd_embed_fwd": (I, [I, P, P, P, P, P, P, I, I, I, I, P]),
     "dtd_embed_fwd_pos": (I, [I, P, P, P, P, P, P, P, I, I, I, I, P]),

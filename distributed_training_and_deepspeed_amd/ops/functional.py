@@ -496,6 +496,127 @@ class CrossEntropyLoss(torch.nn.Module):
 
 
 # --------------------------------------------------------------------------------------
+# LM head + cross-entropy without the logits (ops/csrc/head_xent.hip)
+# --------------------------------------------------------------------------------------
+HEAD_XENT_TILE = 128                 # column tile of the kernels: chunk widths are multiples of it
+HEAD_XENT_MAX_BLOCK = 1 << 30        # rows x chunk width of one block (dtd_head_dlogits_max_elems)
+
+
+def _row_major(t: torch.Tensor) -> bool:
+    return t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]
+
+
+def head_xent_supported(x: torch.Tensor, w: torch.Tensor) -> bool:
+    """True when the gfx950 kernels take this head: bf16 row-major operands on the GPU with
+    16-byte aligned rows and a hidden size the kernels cover (``dtd_head_xent_supported``)."""
+    if not (_on_gpu(x) and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and w.device == x.device):
+        return False
+    if not (_row_major(x) and _row_major(w) and x.shape[1] == w.shape[1]):
+        return False
+    if any(t.data_ptr() % 16 or t.stride(0) % 8 for t in (x, w)):
+        return False
+    return bool(_lib.lib().dtd_head_xent_supported(x.shape[0], w.shape[0], x.shape[1]))
+
+
+def head_xent_ranges(T: int, V: int) -> int:
+    """Vocabulary ranges R of the forward kernel: its partials are ``part [T, R, 2]`` fp32."""
+    return int(_lib.lib().dtd_head_lse_ranges(T, V))
+
+
+def _head_cols(V: int, step: int):
+    return [(v0, min(V, v0 + step)) for v0 in range(0, V, step)]
+
+
+def head_xent_fwd(x: torch.Tensor, w: torch.Tensor, labels: torch.Tensor, ignore_index: int = IGNORE_INDEX,
+                  part: torch.Tensor | None = None):
+    """Mean cross-entropy of ``x [T, h] @ w [V, h]^T`` against ``labels [T]`` without the logits:
+    returns (loss, lse [T], stats [2] = (mean, count)) as ``xent_fwd`` does.  bf16 on the GPU runs
+    ``dtd_head_lse`` (``part``: optional caller-owned [T, R, 2] fp32 partials); anything else runs
+    the same math in fp32 PyTorch over vocabulary chunks, so it never holds [T, V] either."""
+    T, V = x.shape[0], w.shape[0]
+    labels = labels.reshape(-1)
+    if not head_xent_supported(x, w):
+        valid = labels != ignore_index
+        yl = labels.clamp_min(0)
+        xf = x.float()
+        m = torch.full((T,), float("-inf"), dtype=torch.float32, device=x.device)
+        s = torch.zeros(T, dtype=torch.float32, device=x.device)
+        tgt = torch.zeros(T, dtype=torch.float32, device=x.device)
+        for v0, v1 in _head_cols(V, 8192):
+            z = xf @ w[v0:v1].float().t()
+            inside = (yl >= v0) & (yl < v1)
+            tgt = torch.where(inside, z.gather(1, (yl - v0).clamp(0, v1 - v0 - 1)[:, None])[:, 0], tgt)
+            mn = torch.maximum(m, z.max(1).values)
+            s = s * torch.exp(m - mn) + torch.exp(z - mn[:, None]).sum(1)
+            m = mn
+        lse = m + torch.log(s)
+        loss_row = torch.where(valid, lse - tgt, torch.zeros_like(lse))
+        cnt = valid.sum().float()
+        mean = loss_row.sum() / cnt
+        return mean, lse, torch.stack([mean, cnt])
+    labels = labels.contiguous().to(torch.int64)
+    dev = x.device
+    R = head_xent_ranges(T, V)
+    if part is None:
+        part = torch.empty((T, R, 2), dtype=torch.float32, device=dev)
+    assert part.shape == (T, R, 2) and part.is_contiguous() and part.dtype == torch.float32
+    zlab = torch.empty(T, dtype=torch.float32, device=dev)
+    loss_row = torch.empty_like(zlab)
+    lse = torch.empty_like(zlab)
+    stats = torch.empty(2, dtype=torch.float32, device=dev)
+    _lib.call("dtd_head_lse", x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), labels.data_ptr(),
+              part.data_ptr(), zlab.data_ptr(), lse.data_ptr(), loss_row.data_ptr(), stats.data_ptr(), T, V,
+              x.shape[1], ignore_index, _lib.stream())
+    return stats[0], lse, stats
+
+
+def head_xent_dlogits(x: torch.Tensor, w: torch.Tensor, labels: torch.Tensor, lse: torch.Tensor,
+                      stats: torch.Tensor, grad_out: torch.Tensor, v0: int, v1: int,
+                      out: torch.Tensor | None = None, ignore_index: int = IGNORE_INDEX) -> torch.Tensor:
+    """Columns [v0, v1) of dlogits = (softmax - onehot) * valid * grad_out / count, recomputed from
+    x and w with the forward's ``lse``; [T, v1 - v0] in x's dtype.  ``out``: a row-major buffer with
+    at least T rows and v1 - v0 columns (the chunk buffer a caller reuses); the result is its
+    leading view.  grad_out and count are read on the device."""
+    T = x.shape[0]
+    n = v1 - v0
+    labels = labels.reshape(-1)
+    if out is None:
+        out = torch.empty((T, n), dtype=x.dtype, device=x.device)
+    d = out[:T, :n]
+    if (head_xent_supported(x, w) and out.dtype == x.dtype and _row_major(out)
+            and T * out.stride(0) <= HEAD_XENT_MAX_BLOCK and -(-n // HEAD_XENT_TILE) <= 65535):
+        gout = grad_out.reshape(1).to(torch.float32).contiguous()
+        _lib.call("dtd_head_dlogits", x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0),
+                  labels.contiguous().to(torch.int64).data_ptr(), lse.data_ptr(), stats.data_ptr(), gout.data_ptr(),
+                  d.data_ptr(), out.stride(0), T, w.shape[0], x.shape[1], v0, v1, ignore_index, _lib.stream())
+        return d
+    valid = labels != ignore_index
+    p = torch.exp(x.float() @ w[v0:v1].float().t() - lse[:, None])
+    inside = valid & (labels >= v0) & (labels < v1)
+    p[torch.arange(T, device=x.device), (labels - v0).clamp(0, n - 1)] -= inside.float()
+    p = p * (valid.float() * (grad_out.float() / stats[1]))[:, None]
+    d.copy_(torch.where(valid[:, None], p, torch.zeros_like(p)))   # lse is 0 on unlabelled rows: exp may overflow
+    return d
+
+
+def head_xent_plan(T: int, V: int, h: int, chunks: int):
+    """Blocks (r0, r1, v0, v1) of the chunked head backward, covering [0, T) x [0, V) exactly once.
+    Column chunks are ``ceil(V / chunks)`` rounded up to the kernels' 128-column tile (the last one
+    takes the rest); rows are split (on tile boundaries) only when rows x chunk width would pass
+    ``HEAD_XENT_MAX_BLOCK``, the 32-bit addressing limit of the chunk buffer.  Row blocks are the
+    outer loop: one fp32 input-gradient accumulator per row block, one reused chunk buffer."""
+    if T < 1 or V < 1 or chunks < 1:
+        raise ValueError("head_xent_plan: T, V and chunks must be positive")
+    width = -(-(-(-V // chunks)) // HEAD_XENT_TILE) * HEAD_XENT_TILE
+    rows = T
+    if T * width > HEAD_XENT_MAX_BLOCK:
+        rows = max(HEAD_XENT_TILE, HEAD_XENT_MAX_BLOCK // width // HEAD_XENT_TILE * HEAD_XENT_TILE)
+        nrb = -(-T // rows)
+        rows = -(-(-(-T // nrb)) // HEAD_XENT_TILE) * HEAD_XENT_TILE   # even row blocks
+    return [(r0, min(T, r0 + rows), v0, v1) for r0 in range(0, T, rows) for v0, v1 in _head_cols(V, width)]
+
+
+# --------------------------------------------------------------------------------------
 # embeddings
 # --------------------------------------------------------------------------------------
 def embed_fwd(ids: torch.Tensor, word: torch.Tensor, pos: torch.Tensor | None, type_: torch.Tensor | None,

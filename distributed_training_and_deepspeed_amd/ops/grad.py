@@ -200,6 +200,14 @@ def emit_wgrad(p: torch.Tensor, dy: torch.Tensor, x: torch.Tensor, async_ok: boo
     grad_done(p)
 
 
+def wgrad_rows_into(dst: torch.Tensor, acc: bool, r0: int, r1: int, dy: torch.Tensor, x: torch.Tensor) -> None:
+    """dst[r0:r1] (+)= dy^T @ x: the weight gradient of output rows [r0, r1) only; dy [T, r1 - r0]
+    (any row stride), x [T, in].  ``dst`` / ``acc`` come from ONE ``grad_dst(p)`` taken before the
+    first row range, and the caller calls ``grad_done(p)`` once after the last (the chunked LM-head
+    backward: the reducer sees one contribution however many ranges it was written in)."""
+    gemm_into(dst[r0:r1], dy.t(), x, acc)
+
+
 # Token count from which the weight gradients take wgrad.hip (below: hipBLASLt, split-K bmm from
 # 8192, one GEMM under it); DTD_WGRAD_MIN_T.  At the reference's small batches the kernel loses:
 # b4 graph 352-354 k vs 384-385 k tokens/s, bloom-560m b1 37.7 k vs 42.0 k with T >= 512

@@ -58,6 +58,12 @@ def train(model_name, batch_size, training_steps, stage, opts):
     if torch.cuda.is_available():
         from distributed_training_and_deepspeed_amd.utils.tuning import maybe_use_tuned_gemms
         maybe_use_tuned_gemms()   # measured hipBLASLt solutions (incl. this script's default shapes)
+    if opts.fused_head_loss:
+        # Runtime's defaults follow these, so the prewarm model below launches the fused head's
+        # kernels too (before the communicator exists, like every other kernel of the step)
+        os.environ["DTD_HEAD_XENT"] = "1"
+        if opts.head_chunks is not None:
+            os.environ["DTD_HEAD_XENT_CHUNKS"] = str(opts.head_chunks)
     if backend == "nccl" and prewarm_enabled():
         # the step's kernels run once before the RCCL communicator exists: kernels first launched
         # after it run 5-25 % slower for the life of the process (utils/prewarm.py)
@@ -71,6 +77,13 @@ def train(model_name, batch_size, training_steps, stage, opts):
     dtype = {"bf16": torch.bfloat16, "fp32": torch.float32}[opts.dtype]
     cfg = get_config(model_name)
     model = build_model(model_name, dtype=dtype, device=device, seed=0, impl=opts.impl)
+    rt = getattr(model, "rt", None)
+    if rt is not None and opts.fused_head_loss:
+        # the LM-head loss from logit tiles that never reach memory; the backward holds one
+        # vocabulary chunk of dlogits at a time (models/layers.py LMHead.loss)
+        rt.head_loss = "fused"
+    if rt is not None and opts.head_chunks is not None:
+        rt.head_chunks = opts.head_chunks
 
     if opts.graph == "auto":
         # at world > 1 eager by default: the run's comm-latency report (the comms logger times each
@@ -89,6 +102,9 @@ def train(model_name, batch_size, training_steps, stage, opts):
     }
     model_engine, optimizer, _, _ = initialize(model=model, model_parameters=model.parameters(), config=ds_config)
     print(f"Device {rank} - ZeRO Stage: {model_engine.zero_optimization_stage()}")
+    if rt is not None:
+        print(f"Device {rank} - LM head loss: {rt.head_loss}"
+              + (f" ({rt.head_chunks} vocabulary chunks in the backward)" if rt.head_loss == "fused" else ""))
     optimizer_state = optimizer.param_groups[0]
     print(f"Device {rank} - Optimizer: lr={optimizer_state['lr']}; "
           f"betas={optimizer_state['betas']}; eps={optimizer_state['eps']}; "
@@ -201,6 +217,11 @@ if __name__ == "__main__":
     parser.add_argument("--graph", nargs="?", const="on", default="auto", choices=["auto", "on", "off"],
                         help="capture the whole training step in a hipGraph and replay it, at any ZeRO stage "
                              "(auto: on for one GPU, where batch-1 steps are host-launch bound)")
+    parser.add_argument("--fused-head-loss", action="store_true",
+                        help="LM-head loss without the [tokens, vocab] logits and dlogits tensors "
+                             "(Runtime.head_loss = 'fused'; see MEMSTATS for the effect)")
+    parser.add_argument("--head-chunks", type=int, default=None, metavar="N",
+                        help="vocabulary chunks of the fused head backward (default 8)")
     parser.add_argument("--quiet", action="store_true")
     args, extra_args = parser.parse_known_args()
     if args.pack_docs and args.attention_mask:
