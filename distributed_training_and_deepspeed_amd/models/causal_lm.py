@@ -7,7 +7,11 @@ gpt2-medium.  SURVEY.md D17:
   * BLOOM: word embeddings -> embedding LN, pre-LN blocks with fused QKV, ALiBi, tanh-GELU,
     final LN, tied LM head, vocab 250,880 (559,214,592 parameters for bloom-560m);
   * OPT: word + learned positions (offset 2), pre-LN, ReLU, final LN, tied head;
-  * GPT-2: wte + wpe, pre-LN, tanh-GELU, final LN, tied head.
+  * GPT-2: wte + wpe, pre-LN, tanh-GELU, final LN, tied head;
+  * Llama (models/llama.py): word embeddings only, RMSNorm blocks with rotary q / k and a SwiGLU MLP, no
+    biases, final RMSNorm, untied head.  Rotary positions are arange(S), also under ``attention_mask``
+    (as HF's; rotary attention depends only on position differences), and restart at each document
+    with ``segment_ids``.
 Loss: shifted next-token cross entropy (labels = input_ids, ignore_index -100).
 
 ``forward(..., attention_mask=...)`` takes HF's 0/1 ``[B, S]`` key-padding mask (contiguous: left-
@@ -32,7 +36,8 @@ import torch
 from torch import nn
 
 from .config import BLOOM_560M, TransformerConfig, get_config
-from .layers import Embeddings, LayerNorm, LMHead
+from .layers import Embeddings, LayerNorm, LMHead, RMSNorm
+from .llama import LlamaLayer
 from ..ops.attention import doc_position_ids, doc_range_from_segment_ids, key_range_from_mask
 from .transformer import Runtime, TransformerLayer, prefetch_masks, stage_dgrad_transposes
 
@@ -49,8 +54,10 @@ class CausalLM(nn.Module):
         self.config = self.cfg = cfg
         self.rt = rt or Runtime()
         self.embeddings = Embeddings(cfg, self.rt)
-        self.layers = nn.ModuleList([TransformerLayer(cfg, self.rt) for _ in range(cfg.num_layers)])
-        self.final_ln = LayerNorm(cfg.hidden_size, cfg.ln_eps, self.rt) if cfg.final_ln else None
+        layer_cls = LlamaLayer if cfg.llama_style else TransformerLayer
+        norm_cls = RMSNorm if cfg.norm == "rms" else LayerNorm
+        self.layers = nn.ModuleList([layer_cls(cfg, self.rt) for _ in range(cfg.num_layers)])
+        self.final_ln = norm_cls(cfg.hidden_size, cfg.ln_eps, self.rt) if cfg.final_ln else None
         self.head = LMHead(cfg, self.rt, self.embeddings.word)
 
     @classmethod
@@ -62,8 +69,9 @@ class CausalLM(nn.Module):
         return [self.embeddings, *self.layers] + ([self.final_ln] if self.final_ln is not None else [])
 
     def zero3_persistent(self):
-        """Parameters shared between units (LM head tied to the word embeddings)."""
-        return [self.embeddings.word]
+        """Parameters outside the gathered units: the word embeddings the tied LM head shares, or the
+        untied head's own weight (Llama family) -- replicated, with stage-2 treatment of its gradient."""
+        return [self.embeddings.word] if self.head.own_weight is None else [self.head.own_weight]
 
     def encode(self, input_ids: torch.Tensor, attention_mask: torch.Tensor | None = None,
                segment_ids: torch.Tensor | None = None) -> torch.Tensor:
@@ -79,9 +87,17 @@ class CausalLM(nn.Module):
                 raise ValueError(f"segment_ids must be {tuple(input_ids.shape)}, got {tuple(segment_ids.shape)}")
             doc_range = doc_range_from_segment_ids(segment_ids)
             position_ids = doc_position_ids(doc_range)      # restart at every document; pads take 0
+        if self.cfg.rope_theta > 0 and input_ids.shape[1] > self.cfg.max_positions:
+            raise ValueError(f"sequence length {input_ids.shape[1]} exceeds max_positions {self.cfg.max_positions} "
+                             f"(the rotary table)")
         x = self.embeddings(input_ids) if position_ids is None else self.embeddings(input_ids, position_ids=position_ids)
+        # rotary positions restart at each document (one int32 copy serves every layer); arange(S)
+        # otherwise, also under a key-padding mask: rotary attention sees only position differences
+        rope_pos = position_ids.to(torch.int32) if self.cfg.rope_theta > 0 and doc_range is not None else None
         for layer in self.layers:
-            if doc_range is not None:
+            if rope_pos is not None:
+                x = layer(x, doc_range=doc_range, position_ids=rope_pos)
+            elif doc_range is not None:
                 x = layer(x, doc_range=doc_range)
             else:
                 x = layer(x) if key_range is None else layer(x, key_range=key_range)

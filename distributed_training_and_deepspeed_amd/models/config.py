@@ -16,7 +16,7 @@ from dataclasses import asdict, dataclass, field, replace
 @dataclass(frozen=True)
 class TransformerConfig:
     name: str
-    family: str  # "bert" | "bloom" | "opt" | "gpt2" | "block"
+    family: str  # "bert" | "bloom" | "opt" | "gpt2" | "llama" | "block"
     vocab_size: int
     hidden_size: int
     num_layers: int
@@ -25,7 +25,7 @@ class TransformerConfig:
     max_positions: int = 512
     type_vocab_size: int = 0          # BERT token-type embeddings
     position_offset: int = 0          # OPT learned positions are offset by 2
-    activation: str = "gelu"          # "gelu" (erf) | "gelu_tanh" | "relu"
+    activation: str = "gelu"          # "gelu" (erf) | "gelu_tanh" | "relu" | "swiglu" (gated, see below)
     pre_ln: bool = False              # False = post-LN (BERT)
     causal: bool = False
     alibi: bool = False               # BLOOM ALiBi position bias
@@ -40,6 +40,30 @@ class TransformerConfig:
     pad_token_id: int = 0
     special_token_ids: tuple = field(default_factory=tuple)
     mask_token_id: int = -1
+    norm: str = "layer"               # "layer" (LayerNorm) | "rms" (RMSNorm: no mean, no beta)
+    rope_theta: float = 0.0           # rotary position embedding base; 0 = off
+    # activation "swiglu": the gated MLP down(silu(gate(x)) * up(x)), three weights, no bias
+
+    def __post_init__(self):
+        if self.norm not in ("layer", "rms"):
+            raise ValueError(f"norm must be 'layer' or 'rms', got {self.norm!r}")
+        if self.norm == "rms" and self.hidden_dropout > 0:
+            raise ValueError("norm='rms' has no fused residual dropout: hidden_dropout must be 0")
+        if self.rope_theta > 0 and self.alibi:
+            raise ValueError("rope_theta > 0 and alibi are two position schemes: pick one")
+        if self.rope_theta > 0 and self.head_dim not in (64, 128):
+            raise ValueError(f"rotary embeddings need head_dim 64 or 128 (the flash attention kernels), "
+                             f"got {self.head_dim}")
+        if self.activation == "swiglu" and self.bias:
+            raise ValueError("activation='swiglu' is the bias-free gated MLP: bias must be False")
+        traits = (self.norm == "rms", self.rope_theta > 0, self.activation == "swiglu")
+        if any(traits) and not (all(traits) and self.pre_ln and not self.bias):
+            raise ValueError("norm='rms', rope_theta > 0 and activation='swiglu' come together, pre-LN and "
+                             "bias-free (models/llama.py::LlamaLayer is the one layer that implements them)")
+
+    @property
+    def llama_style(self) -> bool:
+        return self.activation == "swiglu"
 
     @property
     def head_dim(self) -> int:
@@ -96,16 +120,35 @@ W4_BLOCK = TransformerConfig(
 CAUSAL_TINY = GPT2_MEDIUM.with_(name="causal-tiny", vocab_size=1024, hidden_size=128,
                                 num_layers=2, num_heads=2, ffn_size=512, max_positions=512)
 
+# Llama family (HF LlamaForCausalLM): RMSNorm, rotary embeddings, SwiGLU MLP, no biases, no position
+# table, untied head.  Multi-head attention only (num_key_value_heads == num_heads): grouped-query
+# checkpoints (Llama-2-70B, Llama-3, TinyLlama) are not described here.  Parameter counts
+# (tests/test_llama_cpu.py): 2 V h + L (4 h^2 + 3 h f + 2 h) + h.
+LLAMA_160M = TransformerConfig(
+    name="JackFram/llama-160m", family="llama", vocab_size=32000, hidden_size=768, num_layers=12,
+    num_heads=12, ffn_size=3072, max_positions=2048, activation="swiglu", pre_ln=True, causal=True,
+    final_ln=True, tie_word_embeddings=False, ln_eps=1e-6, hidden_dropout=0.0, attn_dropout=0.0,
+    bias=False, pad_token_id=0, special_token_ids=(0, 1, 2), norm="rms", rope_theta=10000.0,
+)
+SHEARED_LLAMA_1_3B = LLAMA_160M.with_(name="princeton-nlp/Sheared-LLaMA-1.3B", hidden_size=2048, num_layers=24,
+                                      num_heads=16, ffn_size=5504, max_positions=4096, ln_eps=1e-5)
+LLAMA_2_7B = LLAMA_160M.with_(name="meta-llama/Llama-2-7b-hf", hidden_size=4096, num_layers=32, num_heads=32,
+                              ffn_size=11008, max_positions=4096, ln_eps=1e-5)
+LLAMA_TINY = LLAMA_160M.with_(name="llama-tiny", vocab_size=1024, hidden_size=128, num_layers=2, num_heads=2,
+                              ffn_size=384, max_positions=512)
+
 PRESETS = {
     c.name: c
     for c in (BERT_BASE, BERT_LARGE, BERT_TINY, BLOOM_560M, OPT_125M, GPT2_MEDIUM, W4_BLOCK,
-              CAUSAL_TINY)
+              CAUSAL_TINY, LLAMA_160M, SHEARED_LLAMA_1_3B, LLAMA_2_7B, LLAMA_TINY)
 }
 ALIASES = {
     "base": "bert-base-cased", "large": "bert-large-cased", "tiny": "bert-tiny",
     "bert-base": "bert-base-cased", "bert-large": "bert-large-cased",
     "bloom-560m": "bigscience/bloom-560m", "opt-125m": "facebook/opt-125m",
     "openai-community/gpt2-medium": "gpt2-medium",
+    "llama-160m": "JackFram/llama-160m", "sheared-llama-1.3b": "princeton-nlp/Sheared-LLaMA-1.3B",
+    "llama-2-7b": "meta-llama/Llama-2-7b-hf",
 }
 
 

@@ -10,8 +10,10 @@
   that carry an MLM label (~15% of tokens): the loss and every gradient are mathematically
   identical to the dense head (unlabelled rows contribute exactly zero), it just skips the
   logits that CrossEntropyLoss(ignore_index=-100) would discard.
-* ``LMHead``: tied causal-LM head with the shifted-label cross entropy of HF *ForCausalLM,
-  computed only on the S-1 positions that have a next-token label.  ``Runtime.head_loss =
+* ``RMSNorm``: final norm of the Llama family (ops/csrc/rmsnorm.hip forward/backward).
+* ``LMHead``: causal-LM head -- tied to the word embeddings, or with its own ``[V, h]`` weight when
+  ``tie_word_embeddings`` is off (Llama family) -- with the shifted-label cross entropy of HF
+  *ForCausalLM, computed only on the S-1 positions that have a next-token label.  ``Runtime.head_loss =
   "fused"`` computes it without the [B*S, V] logits and dlogits tensors (ops/csrc/head_xent.hip).
 """
 from __future__ import annotations
@@ -77,6 +79,48 @@ class LayerNorm(nn.Module):
             note_use((self.weight, self.bias))
             return _LNFn.apply(x, self.weight, self.bias, self.eps)
         return F.layer_norm(x, (x.shape[-1],), self.weight, self.bias, self.eps)
+
+
+# ----------------------------------------------------------------------------- RMSNorm
+class _RMSFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, mod, g):
+        h = x.shape[-1]
+        x2 = x.reshape(-1, h)
+        _, out, r = Fx.rms_fwd(None, x2, g, mod.eps)
+        ctx.save_for_backward(x2, r)
+        ctx.mod = mod
+        return out.view_as(x)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x2, r = ctx.saved_tensors
+        g = ctx.mod.weight        # read now: ZeRO-3 may have released and re-gathered it
+        dx = Fx.rms_bwd(dout.reshape(-1, x2.shape[-1]), None, x2, r, g, dgamma=grad_dst(g))
+        grad_done(g)
+        return dx.view_as(dout), None, None
+
+
+def ref_rms_norm(x: torch.Tensor, g: torch.Tensor, eps: float) -> torch.Tensor:
+    """Differentiable RMSNorm in fp32, rounded once (HF LlamaRMSNorm up to where it rounds)."""
+    xf = x.float()
+    return (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * g.float()).to(x.dtype)
+
+
+class RMSNorm(nn.Module):
+    """Final norm of the Llama family: x * rsqrt(mean(x^2) + eps) * weight."""
+
+    def __init__(self, h: int, eps: float, rt: Runtime):
+        super().__init__()
+        self.weight = nn.Parameter(torch.ones(h))
+        self.eps, self.rt = eps, rt
+
+    def forward(self, x):
+        self._dtd_weightless_bwd = self.rt.use_fused(x)   # see TransformerLayer.forward
+        if self._dtd_weightless_bwd:
+            note_use((self.weight,))
+            return _RMSFn.apply(x, self, self.weight)
+        return ref_rms_norm(x, self.weight, self.eps)
 
 
 # ----------------------------------------------------------------------------- Embeddings
@@ -442,11 +486,18 @@ class LMHead(nn.Module):
     def __init__(self, cfg: TransformerConfig, rt: Runtime, word_embeddings: nn.Parameter):
         super().__init__()
         self.cfg, self.rt = cfg, rt
-        self._tied = [word_embeddings]
+        if cfg.tie_word_embeddings:
+            self.own_weight = None
+            self._tied = [word_embeddings]   # list: not registered twice as a parameter
+        else:
+            # HF lm_head.weight of an untied model (the Llama family): [V, h], N(0, 0.02)
+            self.own_weight = nn.Parameter(torch.empty(cfg.vocab_size, cfg.hidden_size))
+            init_linear_(self.own_weight, None)
+            self._tied = None
 
     @property
     def weight(self):
-        return self._tied[0]
+        return self.own_weight if self.own_weight is not None else self._tied[0]
 
     def forward(self, x: torch.Tensor, labels: torch.Tensor | None = None) -> torch.Tensor:
         self._dtd_weightless_bwd = labels is not None and self.rt.use_fused(x)   # TransformerLayer.forward

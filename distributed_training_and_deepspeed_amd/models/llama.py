@@ -1,0 +1,272 @@
+"""Llama-family decoder layer (HF ``LlamaDecoderLayer``, multi-head attention) and HF weight conversion.
+
+    a_in = RMS1(x);  qkv = a_in qkv_w^T;  rotary(q, k);  ctx = causal attention;  o = ctx o_w^T
+    z1 = x + o;  f_in = RMS2(z1);  gu = f_in gu_w^T;  a = silu(gate) * up;  out = z1 + a down_w^T
+
+Two interchangeable implementations, as ``TransformerLayer``:
+
+* ``fused``: one autograd node per layer with a hand-written backward over the gfx950 kernels -- residual +
+  RMSNorm (ops/csrc/rmsnorm.hip), rotary embedding in place on the packed qkv (rope.hip), flash attention,
+  SwiGLU (swiglu.hip) -- and the GEMMs of ops/gemm.py, writing weight gradients straight into the flat
+  gradient buckets.  Saved per layer: x, a_in, the rotated qkv, ctx + LSE, z1, f_in, gu, the two rstd
+  vectors and (``rt.keep_ffn_act``) a.  No cos / sin, no attention scores.  The rotation is orthogonal, so
+  the backward applies the inverse rotation to the attention backward's dqkv before the qkv projection's
+  weight and input gradients.
+* ``reference``: the same math in plain differentiable PyTorch.
+
+Weight layout: ``qkv_w [3h, h]`` is HF's q_proj, k_proj, v_proj rows concatenated, ``gu_w [2f, h]`` its
+gate_proj then up_proj rows, so HF checkpoints convert by ``torch.cat`` (``from_hf_state_dict`` /
+``to_hf_state_dict``; they only rename, concatenate and split -- nothing here reaches a hub).
+
+Grouped-query attention, rotary scaling and a KV cache are not implemented.
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+import torch.nn.functional as F
+from torch import nn
+
+from ..ops import attention as A
+from ..ops import functional as Fx
+from ..ops import gemm as G
+from ..ops.grad import emit_wgrad, grad_done, grad_dst, note_use
+from .config import TransformerConfig
+from .layers import ref_rms_norm
+from .transformer import Runtime, init_linear_, ref_attn_dropout
+
+
+def rope_table_for(rt: Runtime, cfg: TransformerConfig, device) -> torch.Tensor:
+    """The model's (cos, sin) table on ``device``: built once (float64 angles, fp32 [max_positions,
+    D/2, 2]) and kept on the Runtime -- not a buffer, so it stays off the state dict and
+    ``model.to(bfloat16)`` does not round it.  It must exist before a hipGraph capture (the eager
+    warm-up steps build it): building it inside one would tie its memory to the graph's pool."""
+    tables = rt.rope_tables
+    key = (str(torch.device(device)), cfg.head_dim, float(cfg.rope_theta), cfg.max_positions)
+    t = tables.get(key)
+    if t is None:
+        if torch.device(device).type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("the rotary table must be built before a graph capture (run one eager step first)")
+        t = tables[key] = Fx.rope_table(cfg.max_positions, cfg.head_dim, cfg.rope_theta, device=device)
+    return t
+
+
+def _ref_rope(x: torch.Tensor, cs: torch.Tensor) -> torch.Tensor:
+    """Differentiable rotate-half rotary embedding: x [B, S, H, D], cs [B or 1, S, D/2, 2] fp32."""
+    half = x.shape[-1] // 2
+    c, s = cs[..., 0][:, :, None], cs[..., 1][:, :, None]
+    x1, x2 = x[..., :half].float(), x[..., half:].float()
+    return torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], -1).to(x.dtype)
+
+
+class LlamaLayer(nn.Module):
+    def __init__(self, cfg: TransformerConfig, rt: Runtime):
+        super().__init__()
+        if not cfg.llama_style:
+            raise ValueError("LlamaLayer needs norm='rms', rope_theta > 0 and activation='swiglu'")
+        h, f = cfg.hidden_size, cfg.ffn_size
+        self.cfg, self.rt = cfg, rt
+        self.qkv_w = nn.Parameter(torch.empty(3 * h, h))      # q rows, then k, then v
+        self.o_w = nn.Parameter(torch.empty(h, h))
+        self.n1_g = nn.Parameter(torch.ones(h))               # input_layernorm
+        self.gu_w = nn.Parameter(torch.empty(2 * f, h))       # gate rows, then up
+        self.down_w = nn.Parameter(torch.empty(h, f))
+        self.n2_g = nn.Parameter(torch.ones(h))               # post_attention_layernorm
+        for w in (self.qkv_w, self.o_w, self.gu_w, self.down_w):
+            init_linear_(w, None)
+        self.sid_attn = rt.new_sid()
+
+    def params(self):
+        return (self.qkv_w, self.o_w, self.n1_g, self.gu_w, self.down_w, self.n2_g)
+
+    def dgrad_weights(self, nt: bool):
+        """See ``TransformerLayer.dgrad_weights``: the four projections in the NT form; there is no
+        fused FFN-backward GEMM here, so nothing otherwise."""
+        return (self.qkv_w, self.o_w, self.gu_w, self.down_w) if nt else ()
+
+    def prefetch_attention_masks(self, B: int, S: int, device) -> None:
+        """No side-stream mask prefetch: attention dropout (0 in every Llama preset) draws its keep
+        bits inside the attention call."""
+
+    def forward(self, x: torch.Tensor, key_range: torch.Tensor | None = None, doc_range=None,
+                position_ids: torch.Tensor | None = None) -> torch.Tensor:
+        """x: [B, S, h] -> [B, S, h].  ``key_range`` / ``doc_range`` as ``TransformerLayer.forward``.
+        ``position_ids``: optional integer [B, S] rotary position per token (a packed batch restarts
+        them at each document); default s."""
+        if key_range is not None and doc_range is not None:
+            raise ValueError("key_range and doc_range are mutually exclusive")
+        S = x.shape[1]
+        if S > self.cfg.max_positions:
+            raise ValueError(f"sequence length {S} exceeds max_positions {self.cfg.max_positions} of the rotary table")
+        table = rope_table_for(self.rt, self.cfg, x.device)
+        # the fused backward reads the parameters at backward time: see TransformerLayer.forward
+        self._dtd_weightless_bwd = self.rt.use_fused(x)
+        if self._dtd_weightless_bwd:
+            note_use(self.params())
+            return _FusedLlamaLayerFn.apply(x, self, key_range, doc_range, position_ids, table, *self.params())
+        return self._reference(x, key_range, doc_range, position_ids, table)
+
+    # ------------------------------------------------------------------ reference path
+    def _reference(self, x, key_range, doc_range, position_ids, table):
+        c, rt = self.cfg, self.rt
+        B, S, h = x.shape
+        H, D = c.num_heads, c.head_dim
+        tr = self.training
+        p_a = c.attn_dropout if tr else 0.0
+        if position_ids is None:
+            cs = table[:S][None]
+        else:
+            cs = table[position_ids.to(device=x.device, dtype=torch.int64).clamp(0, table.shape[0] - 1)]
+        a_in = ref_rms_norm(x, self.n1_g, c.ln_eps)
+        qkv = F.linear(a_in, self.qkv_w).view(B, S, 3, H, D)
+        q = _ref_rope(qkv[:, :, 0], cs).transpose(1, 2)
+        k = _ref_rope(qkv[:, :, 1], cs).transpose(1, 2)
+        v = qkv[:, :, 2].transpose(1, 2)
+        s = torch.matmul(q, k.transpose(-1, -2)) * (1.0 / math.sqrt(D))
+        if c.causal:
+            s = s.masked_fill(torch.ones(S, S, dtype=torch.bool, device=s.device).triu(1), float("-inf"))
+        if key_range is not None or doc_range is not None:
+            outside = A._range_mask(key_range, B, S, s.device) if key_range is not None \
+                else A._doc_mask(doc_range, B, S, s.device)
+            s = s.masked_fill(outside, float("-inf"))
+            # a row without a key (all -inf, softmax NaN) attends to nothing: probabilities 0
+            dead = (s == float("-inf")).all(-1, keepdim=True)
+            prob = torch.softmax(s.float().masked_fill(dead, 0.0), -1).masked_fill(dead, 0.0).to(s.dtype)
+        else:
+            prob = torch.softmax(s.float(), -1).to(s.dtype)
+        prob = ref_attn_dropout(prob, p_a, tr, rt, rt.rng.sid(self.sid_attn))
+        ctx = torch.matmul(prob, v).transpose(1, 2).reshape(B, S, h)
+        z1 = x + F.linear(ctx, self.o_w)
+        f_in = ref_rms_norm(z1, self.n2_g, c.ln_eps)
+        g, u = F.linear(f_in, self.gu_w).split(c.ffn_size, -1)
+        return z1 + F.linear(F.silu(g) * u, self.down_w)
+
+
+_dgrad = G.dgrad
+
+
+def _linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """Bias-free projection: the GEMM dispatch of ops/gemm.py on the GPU, F.linear on the CPU."""
+    return G.linear_any(x, w) if x.is_cuda else F.linear(x, w)
+
+
+class _FusedLlamaLayerFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, layer: LlamaLayer, key_range, doc_range, position_ids, table, *params):
+        c, rt = layer.cfg, layer.rt
+        (qkv_w, o_w, g1, gu_w, down_w, g2) = params
+        B, S, h = x.shape
+        H, D = c.num_heads, c.head_dim
+        T = B * S
+        p_a = c.attn_dropout if layer.training else 0.0
+        rng = rt.rng
+        sa = rng.sid(layer.sid_attn)
+        x2d = x.reshape(T, h)
+        eps = c.ln_eps
+        _, a_in, r1 = Fx.rms_fwd(None, x2d, g1, eps)
+        qkv = _linear(a_in, qkv_w)
+        Fx.rope_(qkv, table, B, S, H, D, pos=position_ids)     # in place: the rotated qkv is what is kept
+        actx, lse, amask = A.attn_fwd(qkv, B, S, H, D, c.causal, None, p_a, rng, sa,
+                                      key_range=key_range, doc_range=doc_range)
+        o = _linear(actx, o_w)
+        z1, f_in, r2 = Fx.rms_fwd(o, x2d, g2, eps)             # z1 = x + o and RMS2(z1) in one pass
+        gu = _linear(f_in, gu_w)
+        a = Fx.swiglu_fwd(gu)
+        y = _linear(a, down_w)
+        out = Fx.dropout_add(y, z1, 0.0, rng, 0)
+        ctx.save_for_backward(x2d, a_in, qkv, actx, lse, z1, f_in, gu, r1, r2, a if rt.keep_ffn_act else None)
+        ctx.layer = layer
+        ctx.amask = amask
+        ctx.key_range, ctx.doc_range, ctx.position_ids, ctx.table = key_range, doc_range, position_ids, table
+        ctx.rng = rng
+        ctx.meta = (B, S, h, H, D, p_a, sa)
+        return out.view(B, S, h)
+
+    @staticmethod
+    def backward(ctx, dout):
+        layer = ctx.layer
+        c, rng = layer.cfg, ctx.rng
+        B, S, h, H, D, p_a, sa = ctx.meta
+        T = B * S
+        (qkv_w, o_w, g1, gu_w, down_w, g2) = layer.params()
+        pend, layer.rt.pending_wt = layer.rt.pending_wt, None
+        if pend:   # first layer backward of the step: every layer's W^T in one launch
+            G.prepare_transposes(pend)
+        dout = dout.reshape(T, h).contiguous()
+        x2d, a_in, qkv, actx, lse, z1, f_in, gu, r1, r2, a = ctx.saved_tensors
+        # out = z1 + a down_w^T
+        da = _dgrad(dout, down_w)
+        if a is None:    # a = silu(gate) * up rewritten inside the SwiGLU backward pass
+            dgu, a = Fx.swiglu_bwd(da, gu, want_act=True)
+        else:
+            dgu = Fx.swiglu_bwd(da, gu)
+        del da
+        emit_wgrad(down_w, dout, a, async_ok=True)
+        del a
+        emit_wgrad(gu_w, dgu, f_in, async_ok=True)
+        dfin = _dgrad(dgu, gu_w)
+        # f_in = RMS2(z1) and z1 is also out's residual: dz1 = RMS2'(dfin) + dout; z1 = x + o, so dz1
+        # is both o's gradient and the residual term of dx
+        dz1 = Fx.rms_bwd(dfin, dout, z1, r2, g2, dgamma=grad_dst(g2))
+        grad_done(g2)
+        emit_wgrad(o_w, dz1, actx, async_ok=True)
+        dctx = _dgrad(dz1, o_w)
+        dqkv = A.attn_bwd(dctx, qkv, actx, lse, B, S, H, D, c.causal, None, p_a, rng, sa, ctx.amask,
+                          key_range=ctx.key_range, doc_range=ctx.doc_range)
+        # the rotation's adjoint is its inverse: dqkv back in front of the rotary embedding
+        Fx.rope_(dqkv, ctx.table, B, S, H, D, pos=ctx.position_ids, inverse=True)
+        emit_wgrad(qkv_w, dqkv, a_in, async_ok=True)
+        dain = _dgrad(dqkv, qkv_w)
+        dx = Fx.rms_bwd(dain, dz1, x2d, r1, g1, dgamma=grad_dst(g1))
+        grad_done(g1)
+        return (dx.view(B, S, h), None, None, None, None, None) + (None,) * 6
+
+
+# ---------------------------------------------------------------------------------- HF weight conversion
+_HF_LAYER = "model.layers.{i}."
+
+
+def from_hf_state_dict(sd: dict) -> dict:
+    """HF ``LlamaForCausalLM`` state dict -> ``CausalLM`` (Llama family) state dict: keys renamed,
+    q/k/v and gate/up concatenated along the output rows.  ``rotary_emb.inv_freq`` buffers of older
+    checkpoints are dropped; a tied checkpoint (no ``lm_head.weight``) gets the embedding table."""
+    out = {"embeddings.word": sd["model.embed_tokens.weight"],
+           "final_ln.weight": sd["model.norm.weight"],
+           "head.own_weight": sd["lm_head.weight"] if "lm_head.weight" in sd else sd["model.embed_tokens.weight"]}
+    i = 0
+    while _HF_LAYER.format(i=i) + "input_layernorm.weight" in sd:
+        p, q = _HF_LAYER.format(i=i), f"layers.{i}."
+        att, mlp = p + "self_attn.", p + "mlp."
+        out[q + "qkv_w"] = torch.cat([sd[att + "q_proj.weight"], sd[att + "k_proj.weight"], sd[att + "v_proj.weight"]], 0)
+        out[q + "o_w"] = sd[att + "o_proj.weight"]
+        out[q + "n1_g"] = sd[p + "input_layernorm.weight"]
+        out[q + "gu_w"] = torch.cat([sd[mlp + "gate_proj.weight"], sd[mlp + "up_proj.weight"]], 0)
+        out[q + "down_w"] = sd[mlp + "down_proj.weight"]
+        out[q + "n2_g"] = sd[p + "post_attention_layernorm.weight"]
+        if out[q + "qkv_w"].shape[0] != 3 * out[q + "o_w"].shape[0]:
+            raise ValueError("grouped-query checkpoints (fewer key/value heads than query heads) are not supported")
+        i += 1
+    if i == 0:
+        raise ValueError("not a Llama state dict: no model.layers.0.input_layernorm.weight")
+    return out
+
+
+def to_hf_state_dict(sd: dict) -> dict:
+    """The inverse of ``from_hf_state_dict``: split qkv_w into q/k/v and gu_w into gate/up."""
+    out = {"model.embed_tokens.weight": sd["embeddings.word"], "model.norm.weight": sd["final_ln.weight"],
+           "lm_head.weight": sd["head.own_weight"]}
+    i = 0
+    while f"layers.{i}.qkv_w" in sd:
+        p, q = _HF_LAYER.format(i=i), f"layers.{i}."
+        att, mlp = p + "self_attn.", p + "mlp."
+        qw, kw, vw = sd[q + "qkv_w"].chunk(3, 0)
+        gw, uw = sd[q + "gu_w"].chunk(2, 0)
+        out[att + "q_proj.weight"], out[att + "k_proj.weight"], out[att + "v_proj.weight"] = qw, kw, vw
+        out[att + "o_proj.weight"] = sd[q + "o_w"]
+        out[p + "input_layernorm.weight"] = sd[q + "n1_g"]
+        out[mlp + "gate_proj.weight"], out[mlp + "up_proj.weight"] = gw, uw
+        out[mlp + "down_proj.weight"] = sd[q + "down_w"]
+        out[p + "post_attention_layernorm.weight"] = sd[q + "n2_g"]
+        i += 1
+    return out

@@ -69,6 +69,8 @@ class Runtime:
         # reused chunk of dlogits.  See LMHead.loss.
         self.head_loss = "fused" if os.environ.get("DTD_HEAD_XENT", "0") == "1" else "logits"
         self.head_chunks = int(os.environ.get("DTD_HEAD_XENT_CHUNKS", "8"))
+        # rotary (cos, sin) tables of the model, one per device (models/llama.py::rope_table_for)
+        self.rope_tables: dict = {}
 
     def new_sid(self) -> int:
         """Dropout stream id for one call site; deterministic per model structure so two
@@ -97,11 +99,8 @@ def stage_dgrad_transposes(layers, x: torch.Tensor) -> None:
     if layers[0].training and torch.is_grad_enabled() and x.is_cuda and rt.use_fused(x):
         # which W^T the backward will read: every projection's in the NT input-gradient form, else
         # only fc2's (the fused FFN-backward GEMM, which needs the kept activation)
-        if G.dgrad_nt_enabled():
-            names = ("qkv_w", "o_w", "fc1_w", "fc2_w")
-        else:
-            names = ("fc2_w",) if rt.keep_ffn_act else ()
-        rt.pending_wt = [getattr(layer, n) for layer in layers for n in names] or None
+        nt = G.dgrad_nt_enabled()
+        rt.pending_wt = [w for layer in layers for w in layer.dgrad_weights(nt)] or None
 
 
 def prefetch_masks(layers, input_ids: torch.Tensor) -> None:
@@ -136,6 +135,8 @@ def ref_attn_dropout(prob, p, training, rt: Runtime, sid):
 class TransformerLayer(nn.Module):
     def __init__(self, cfg: TransformerConfig, rt: Runtime):
         super().__init__()
+        if cfg.llama_style:
+            raise ValueError("RMSNorm / rotary / SwiGLU configurations are built from models.llama.LlamaLayer")
         h, f = cfg.hidden_size, cfg.ffn_size
         self.cfg, self.rt = cfg, rt
         self._prefetched = None  # (sid, B, S, PendingMasks) from prefetch_attention_masks
@@ -173,6 +174,14 @@ class TransformerLayer(nn.Module):
     def params(self):
         return (self.qkv_w, self.qkv_b, self.o_w, self.o_b, self.ln1_g, self.ln1_b,
                 self.fc1_w, self.fc1_b, self.fc2_w, self.fc2_b, self.ln2_g, self.ln2_b)
+
+    def dgrad_weights(self, nt: bool):
+        """The weights whose transposes this layer's backward reads (``stage_dgrad_transposes``):
+        every projection's in the NT input-gradient form (``nt``), else only fc2's (the fused
+        FFN-backward GEMM, which needs the kept activation)."""
+        if nt:
+            return (self.qkv_w, self.o_w, self.fc1_w, self.fc2_w)
+        return (self.fc2_w,) if self.rt.keep_ffn_act else ()
 
     def prefetch_attention_masks(self, B: int, S: int, device) -> None:
         """Start generating this layer's attention-dropout keep bits now, on the side stream.

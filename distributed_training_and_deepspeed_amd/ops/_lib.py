@@ -35,6 +35,16 @@ _SIGS = {
     "dtd_ln_fwd": (I, [I, P, P, P, P, P, P, P, P, I, I, F, F, P, U32, P]),
     "dtd_ln_bwd": (I, [I, P, P, P, P, P, P, P, P, P, P, P, P, I, I, F, P, U32, P]),
     "dtd_ln_bwd_fo": (I, [I, P, P, P, P, P, P, P, P, P, P, P, P, I, I, F, P, U32, P]),
+    # rmsnorm.hip
+    "dtd_rms_supported": (I, [I]),
+    "dtd_rms_bwd_num_partials": (I, [I, I]),
+    "dtd_rms_fwd": (I, [I, P, P, P, P, P, P, I, I, F, P]),
+    "dtd_rms_bwd": (I, [I, P, P, P, P, P, P, P, P, I, I, P]),
+    # rope.hip
+    "dtd_rope": (I, [I, P, P, P, I, I, I, I, L, I, I, P]),
+    # swiglu.hip
+    "dtd_swiglu_fwd": (I, [I, P, P, I, I, P]),
+    "dtd_swiglu_bwd": (I, [I, P, P, P, P, I, I, P]),
     # act.hip
     "dtd_act_fwd": (I, [I, P, P, SZ, I, P]),
     "dtd_act_bwd_num_partials": (I, [I, I]),

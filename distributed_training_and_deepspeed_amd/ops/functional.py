@@ -361,6 +361,161 @@ def bias_grad(dy: torch.Tensor, dbias: torch.Tensor, acc: bool = False) -> None:
 
 
 # --------------------------------------------------------------------------------------
+# Llama-family ops: residual + RMSNorm, rotary embedding, SwiGLU (ops/csrc/rmsnorm.hip, rope.hip,
+# swiglu.hip).  Each runs its kernel for bf16 / fp32 tensors on the GPU and the same math in fp32
+# PyTorch elsewhere (CPU, a shape the kernels do not take, or a library built before they existed).
+# --------------------------------------------------------------------------------------
+def _kernel_dtype(t: torch.Tensor) -> bool:
+    return _on_gpu(t) and t.dtype in (torch.bfloat16, torch.float32)
+
+
+def _rms_kernel(t: torch.Tensor, h: int) -> bool:
+    return _kernel_dtype(t) and _lib.has("dtd_rms_fwd") and bool(_lib.lib().dtd_rms_supported(h))
+
+
+def rms_fwd(y, r, gamma, eps: float):
+    """z = r + y (either may be None); out = z * rsqrt(mean(z^2) + eps) * gamma, in fp32, rounded
+    once.  Returns (z, out, rstd); z is None unless both y and r are given (it is then an input)."""
+    ref = y if y is not None else r
+    h = ref.shape[-1]
+    rows = ref.numel() // h
+    both = y is not None and r is not None
+    if not _rms_kernel(ref, h):
+        zf = ref.float() if not both else y.float() + r.float()
+        z2 = zf.reshape(rows, h)
+        rstd = torch.rsqrt(z2.pow(2).mean(-1) + eps)
+        out = (z2 * rstd[:, None] * gamma.float()).to(ref.dtype).view_as(ref)
+        return (zf.to(ref.dtype) if both else None), out, rstd
+    y, r, gamma = _c(y), _c(r), gamma.contiguous()
+    assert gamma.dtype == ref.dtype and (not both or (y.shape == r.shape and y.dtype == r.dtype))
+    z = torch.empty_like(ref) if both else None
+    out = torch.empty_like(ref)
+    rstd = torch.empty(rows, dtype=torch.float32, device=ref.device)
+    _lib.call("dtd_rms_fwd", _lib.dt(ref), _lib.ptr(y), _lib.ptr(r), gamma.data_ptr(), _lib.ptr(z), out.data_ptr(),
+              rstd.data_ptr(), rows, h, float(eps), _lib.stream())
+    return z, out, rstd
+
+
+def rms_bwd(dout, dz_extra, z, rstd, gamma, dgamma=None, acc: bool = False, dout2=None):
+    """Backward of ``rms_fwd`` for its input sum z: g = (dout + dout2) * gamma, x-hat = z * rstd,
+    dz = rstd * (g - x-hat * mean(g * x-hat)) + dz_extra.  Writes the column sums of
+    (dout + dout2) * x-hat into ``dgamma`` (a tensor with ``acc``, or a (tensor, acc) pair) through
+    fp32 per-block partials and the deterministic column-sum finalize."""
+    h = dout.shape[-1]
+    rows = dout.numel() // h
+    if not _rms_kernel(dout, h):
+        d = dout.float().reshape(rows, h)
+        if dout2 is not None:
+            d = d + dout2.float().reshape(rows, h)
+        xh = z.float().reshape(rows, h) * rstd[:, None]
+        g = d * gamma.float()
+        dz = rstd[:, None] * (g - xh * (g * xh).mean(-1, keepdim=True))
+        if dz_extra is not None:
+            dz = dz + dz_extra.float().reshape(rows, h)
+        _write_grad(dgamma, (d * xh).sum(0), acc)
+        return dz.to(dout.dtype).view_as(dout)
+    dout, dz_extra, dout2, z, gamma = _c(dout), _c(dz_extra), _c(dout2), z.contiguous(), gamma.contiguous()
+    assert z.dtype == dout.dtype and z.numel() == dout.numel() and gamma.dtype == dout.dtype
+    dz = torch.empty_like(dout)
+    part = None
+    if dgamma is not None:
+        n = _lib.lib().dtd_rms_bwd_num_partials(rows, h)
+        part = torch.empty((n, h), dtype=torch.float32, device=dout.device)
+    _lib.call("dtd_rms_bwd", _lib.dt(dout), dout.data_ptr(), _lib.ptr(dout2), _lib.ptr(dz_extra), z.data_ptr(),
+              rstd.data_ptr(), gamma.data_ptr(), dz.data_ptr(), _lib.ptr(part), rows, h, _lib.stream())
+    if part is not None:
+        _finalize(part, n, h, dgamma, acc)
+    return dz
+
+
+def rope_table(max_positions: int, head_dim: int, theta: float = 10000.0, device="cpu") -> torch.Tensor:
+    """(cos, sin) of p * theta^(-2j/D) for p < max_positions, j < D/2: fp32 [max_positions, D/2, 2],
+    rounded once from float64 angles."""
+    if head_dim % 2:
+        raise ValueError("rope_table: head_dim must be even")
+    j = torch.arange(head_dim // 2, dtype=torch.float64)
+    inv = torch.pow(torch.tensor(float(theta), dtype=torch.float64), -2.0 * j / head_dim)
+    ang = torch.arange(max_positions, dtype=torch.float64)[:, None] * inv[None]
+    return torch.stack([ang.cos(), ang.sin()], -1).to(torch.float32).to(device).contiguous()
+
+
+def rope_(qkv: torch.Tensor, table: torch.Tensor, B: int, S: int, H: int, D: int, pos: torch.Tensor | None = None,
+          inverse: bool = False) -> torch.Tensor:
+    """Rotate the q and k slices of the packed ``qkv [B*S, 3*H*D]`` IN PLACE (HF's rotate-half
+    convention; v untouched) and return it.  ``table``: ``rope_table`` on qkv's device.  ``pos``:
+    optional integer [B, S] position per token (default s).  ``inverse`` negates the sine: the inverse
+    rotation, which is also the adjoint -- the backward is ``rope_(dqkv, ..., inverse=True)``."""
+    if qkv.dim() != 2 or qkv.shape[0] != B * S or qkv.shape[1] != 3 * H * D or qkv.stride(1) != 1:
+        raise ValueError(f"rope_: qkv must be [B*S, 3*H*D] = [{B * S}, {3 * H * D}], got {tuple(qkv.shape)}")
+    if tuple(table.shape[1:]) != (D // 2, 2) or table.dtype != torch.float32 or table.device != qkv.device:
+        raise ValueError("rope_: table must be rope_table(max_positions, D) (fp32 [P, D/2, 2]) on qkv's device")
+    if pos is None and S > table.shape[0]:
+        raise ValueError(f"rope_: sequence length {S} exceeds the table's {table.shape[0]} positions")
+    if pos is not None and pos.numel() != B * S:
+        raise ValueError("rope_: pos needs one position per token")
+    if _kernel_dtype(qkv) and D % 16 == 0 and qkv.stride(0) % 8 == 0 and qkv.data_ptr() % 16 == 0 \
+            and _lib.has("dtd_rope"):
+        table = table.contiguous()
+        p32 = pos.reshape(-1).to(device=qkv.device, dtype=torch.int32).contiguous() if pos is not None else None
+        _lib.call("dtd_rope", _lib.dt(qkv), qkv.data_ptr(), table.data_ptr(), _lib.ptr(p32), B, S, H, D,
+                  qkv.stride(0), table.shape[0], int(inverse), _lib.stream())
+        return qkv
+    if pos is None:
+        idx = torch.arange(S, device=qkv.device).repeat(B)
+    else:
+        idx = pos.reshape(-1).to(device=qkv.device, dtype=torch.int64).clamp(0, table.shape[0] - 1)
+    cs = table[idx]                                    # [B*S, D/2, 2]
+    c, s = cs[:, None, :, 0], cs[:, None, :, 1]
+    if inverse:
+        s = -s
+    x = qkv[:, :2 * H * D].reshape(B * S, 2 * H, D).float()
+    x1, x2 = x[..., :D // 2], x[..., D // 2:]
+    out = torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], -1)
+    qkv[:, :2 * H * D] = out.reshape(B * S, 2 * H * D).to(qkv.dtype)
+    return qkv
+
+
+def _swiglu_kernel(t: torch.Tensor, f: int) -> bool:
+    return _kernel_dtype(t) and f % 8 == 0 and _lib.has("dtd_swiglu_fwd")
+
+
+def swiglu_fwd(gu: torch.Tensor) -> torch.Tensor:
+    """a = silu(gate) * up for ``gu [rows, 2f]`` = (gate | up)."""
+    f = gu.shape[-1] // 2
+    if gu.shape[-1] != 2 * f:
+        raise ValueError("swiglu_fwd: gu needs an even number of columns (gate | up)")
+    rows = gu.numel() // (2 * f)
+    if not _swiglu_kernel(gu, f):
+        g, u = gu.float().split(f, -1)
+        return (g * torch.sigmoid(g) * u).to(gu.dtype)
+    gu = gu.contiguous()
+    a = torch.empty(gu.shape[:-1] + (f,), dtype=gu.dtype, device=gu.device)
+    _lib.call("dtd_swiglu_fwd", _lib.dt(gu), gu.data_ptr(), a.data_ptr(), rows, f, _lib.stream())
+    return a
+
+
+def swiglu_bwd(da: torch.Tensor, gu: torch.Tensor, want_act: bool = False):
+    """dgu = (dgate | dup) with dgate = da * up * sig(g) * (1 + g * (1 - sig(g))) and
+    dup = da * silu(g).  ``want_act``: also return a = silu(gate) * up, rewritten in the same pass
+    (bitwise the forward's) -> (dgu, a)."""
+    f = gu.shape[-1] // 2
+    rows = gu.numel() // (2 * f)
+    if not _swiglu_kernel(gu, f):
+        g, u = gu.float().split(f, -1)
+        sg = torch.sigmoid(g)
+        d = da.float()
+        dgu = torch.cat([d * u * sg * (1 + g * (1 - sg)), d * (g * sg)], -1).to(gu.dtype)
+        return (dgu, swiglu_fwd(gu)) if want_act else dgu
+    gu, da = gu.contiguous(), da.contiguous()
+    assert da.dtype == gu.dtype and da.numel() == rows * f
+    dgu = torch.empty_like(gu)
+    a = torch.empty_like(da) if want_act else None
+    _lib.call("dtd_swiglu_bwd", _lib.dt(gu), da.data_ptr(), gu.data_ptr(), dgu.data_ptr(), _lib.ptr(a), rows, f,
+              _lib.stream())
+    return (dgu, a) if want_act else dgu
+
+
+# --------------------------------------------------------------------------------------
 # softmax cross-entropy
 # --------------------------------------------------------------------------------------
 def xent_fwd(logits: torch.Tensor, labels: torch.Tensor, ignore_index: int = IGNORE_INDEX):
