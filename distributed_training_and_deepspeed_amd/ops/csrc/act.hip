@@ -56,7 +56,9 @@ __device__ __forceinline__ float act_df(float x) {
   } else if constexpr (ACT == kGeluTanh) {
     const float k = 0.7978845608028654f;
     const float t = fast_tanh(k * fmaf(0.044715f * x, x * x, x));
-    return 0.5f * (1.f + t) + 0.5f * x * (1.f - t * t) * k * (1.f + 3.f * 0.044715f * x * x);
+    // x^2 capped below the fp32 overflow: past |x| ~ 1.8e19 the saturated (1 - t^2) = 0 met an infinite
+    // polynomial factor and the derivative was NaN instead of 0 or 1
+    return 0.5f * (1.f + t) + 0.5f * x * (1.f - t * t) * k * (1.f + 3.f * 0.044715f * fminf(x * x, 1e30f));
   } else if constexpr (ACT == kRelu) {
     return x > 0.f ? 1.f : 0.f;
   } else {

@@ -8,6 +8,8 @@
 // One 64-lane wave per row; lanes stride the row in VEC-element (16 B for bf16x8) vectors.
 // Rows up to 64*VEC*KMAX elements stay in registers (one HBM read, one write); wider rows take
 // an online-softmax pass (running max/sum) and a second normalising pass.
+#include <float.h>
+
 #include "common.h"
 
 using namespace dtd;
@@ -59,8 +61,11 @@ __global__ void __launch_bounds__(256) softmax_fwd_kernel(const T* __restrict__ 
     }
     return;
   }
-  // wide rows: online max / sum, then normalise
-  float m = -INFINITY, s = 0.f;
+  // wide rows: online max / sum, then normalise.  The running max starts at the lowest finite
+  // float, not -inf: a chunk of -inf (masked) inputs met before the lane's first finite one then
+  // gives exp(m - nm) = 1 and adds exp(-inf - nm) = 0, where -inf - -inf was NaN.  With s = 0 the
+  // first rescale is 0 either way, so finite rows are bitwise what they were.
+  float m = -FLT_MAX, s = 0.f;
   for (int c = lane * VEC; c < n; c += step) {
     float t[VEC];
     vload<T, VEC>(xr + c, t);

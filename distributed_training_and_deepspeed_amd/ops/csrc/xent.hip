@@ -10,6 +10,8 @@
 // an odd vocabulary (GPT-2, 50257) starts at any 2-byte boundary, so each row is split into a
 // scalar head up to the next 16-byte boundary, an aligned 16-byte body and a scalar tail (the
 // first version fell back to 2-byte loads for odd V and ran at ~1.8 TB/s).
+#include <float.h>
+
 #include "common.h"
 
 using namespace dtd;
@@ -39,7 +41,10 @@ __global__ void __launch_bounds__(256) xent_fwd_kernel(const T* __restrict__ log
   const T* z = logits + (size_t)row * V;
   int head, body;
   row_split<T, VEC>(z, V, head, body);
-  float m = -INFINITY, s = 0.f;
+  // The running max starts at the lowest finite float, not -inf: a -inf (masked) logit met before
+  // the thread's first finite one then adds exp(-inf - m) = 0 instead of exp(-inf - -inf) = NaN.
+  // With s = 0 the first rescale is 0 either way, so finite rows are bitwise what they were.
+  float m = -FLT_MAX, s = 0.f;
   auto add1 = [&](float t) {
     if (t > m) { s *= __expf(m - t); m = t; }
     s += __expf(t - m);
@@ -58,7 +63,12 @@ __global__ void __launch_bounds__(256) xent_fwd_kernel(const T* __restrict__ log
   }
   for (int c = body + threadIdx.x; c < V; c += blockDim.x) add1((float)z[c]);
   const float M = block_max(m, sh);
-  s = (m == -INFINITY) ? 0.f : s * __expf(m - M);
+  {
+    // m <= M: a thread that met no finite logit has s = 0 and adds nothing.  Contraction off: fused
+    // into the first add of the block sum, the product would round differently than it always has.
+#pragma clang fp contract(off)
+    s = s * __expf(m - M);
+  }
   const float S = block_sum(s, sh);
   if (threadIdx.x == 0) {
     const float lse = M + __logf(S);

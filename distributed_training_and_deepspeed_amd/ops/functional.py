@@ -312,7 +312,7 @@ def _ref_act_grad(u: torch.Tensor, act: str) -> torch.Tensor:
     if act == "gelu_tanh":
         k = 0.7978845608028654
         t = torch.tanh(k * (x + 0.044715 * x ** 3))
-        return 0.5 * (1 + t) + 0.5 * x * (1 - t * t) * k * (1 + 3 * 0.044715 * x * x)
+        return 0.5 * (1 + t) + 0.5 * x * (1 - t * t) * k * (1 + 3 * 0.044715 * (x * x).clamp_max(1e30))
     if act == "relu":
         return (x > 0).float()
     return torch.ones_like(x)
