@@ -42,6 +42,7 @@ class TransformerConfig:
     mask_token_id: int = -1
     norm: str = "layer"               # "layer" (LayerNorm) | "rms" (RMSNorm: no mean, no beta)
     rope_theta: float = 0.0           # rotary position embedding base; 0 = off
+    num_kv_heads: int = 0             # grouped-query attention (Llama family): key/value heads; 0 = num_heads
     # activation "swiglu": the gated MLP down(silu(gate(x)) * up(x)), three weights, no bias
 
     def __post_init__(self):
@@ -60,6 +61,19 @@ class TransformerConfig:
         if any(traits) and not (all(traits) and self.pre_ln and not self.bias):
             raise ValueError("norm='rms', rope_theta > 0 and activation='swiglu' come together, pre-LN and "
                              "bias-free (models/llama.py::LlamaLayer is the one layer that implements them)")
+
+        if self.num_kv_heads < 0 or (self.num_kv_heads and self.num_heads % self.num_kv_heads):
+            raise ValueError(f"num_kv_heads = {self.num_kv_heads} must divide num_heads = {self.num_heads}")
+        if self.kv_heads != self.num_heads and not self.llama_style:
+            raise ValueError("grouped-query attention (num_kv_heads != num_heads) is implemented by "
+                             "models/llama.py::LlamaLayer only")
+        if self.kv_heads != self.num_heads and self.attn_dropout > 0:
+            raise ValueError("grouped-query attention has no attention dropout: attn_dropout must be 0")
+
+    @property
+    def kv_heads(self) -> int:
+        """Key/value heads: ``num_kv_heads``, or ``num_heads`` when that is 0 (multi-head attention)."""
+        return self.num_kv_heads or self.num_heads
 
     @property
     def llama_style(self) -> bool:
@@ -121,9 +135,10 @@ CAUSAL_TINY = GPT2_MEDIUM.with_(name="causal-tiny", vocab_size=1024, hidden_size
                                 num_layers=2, num_heads=2, ffn_size=512, max_positions=512)
 
 # Llama family (HF LlamaForCausalLM): RMSNorm, rotary embeddings, SwiGLU MLP, no biases, no position
-# table, untied head.  Multi-head attention only (num_key_value_heads == num_heads): grouped-query
-# checkpoints (Llama-2-70B, Llama-3, TinyLlama) are not described here.  Parameter counts
-# (tests/test_llama_cpu.py): 2 V h + L (4 h^2 + 3 h f + 2 h) + h.
+# table, untied head.  num_kv_heads < num_heads: grouped-query attention (TinyLlama, Llama-3).  Parameter
+# counts (tests/test_llama_cpu.py, tests/test_gqa_cpu.py): 2 V h + L (2 h^2 + 2 h Hkv D + 3 h f + 2 h) + h,
+# with Hkv D = h for multi-head attention.  Llama-3.1 / 3.2 (rotary scaling) and Mistral (sliding window)
+# are not described here.
 LLAMA_160M = TransformerConfig(
     name="JackFram/llama-160m", family="llama", vocab_size=32000, hidden_size=768, num_layers=12,
     num_heads=12, ffn_size=3072, max_positions=2048, activation="swiglu", pre_ln=True, causal=True,
@@ -136,11 +151,20 @@ LLAMA_2_7B = LLAMA_160M.with_(name="meta-llama/Llama-2-7b-hf", hidden_size=4096,
                               ffn_size=11008, max_positions=4096, ln_eps=1e-5)
 LLAMA_TINY = LLAMA_160M.with_(name="llama-tiny", vocab_size=1024, hidden_size=128, num_layers=2, num_heads=2,
                               ffn_size=384, max_positions=512)
+# grouped-query attention
+TINYLLAMA_1_1B = LLAMA_160M.with_(name="TinyLlama/TinyLlama_v1.1", hidden_size=2048, num_layers=22, num_heads=32,
+                                  num_kv_heads=4, ffn_size=5632, max_positions=2048, ln_eps=1e-5)
+LLAMA_3_8B = LLAMA_160M.with_(name="meta-llama/Meta-Llama-3-8B", vocab_size=128256, hidden_size=4096, num_layers=32,
+                              num_heads=32, num_kv_heads=8, ffn_size=14336, max_positions=8192, ln_eps=1e-5,
+                              rope_theta=500000.0)
+LLAMA_TINY_GQA = LLAMA_160M.with_(name="llama-tiny-gqa", vocab_size=1024, hidden_size=256, num_layers=2, num_heads=4,
+                                  num_kv_heads=2, ffn_size=768, max_positions=512)
 
 PRESETS = {
     c.name: c
     for c in (BERT_BASE, BERT_LARGE, BERT_TINY, BLOOM_560M, OPT_125M, GPT2_MEDIUM, W4_BLOCK,
-              CAUSAL_TINY, LLAMA_160M, SHEARED_LLAMA_1_3B, LLAMA_2_7B, LLAMA_TINY)
+              CAUSAL_TINY, LLAMA_160M, SHEARED_LLAMA_1_3B, LLAMA_2_7B, LLAMA_TINY, TINYLLAMA_1_1B, LLAMA_3_8B,
+              LLAMA_TINY_GQA)
 }
 ALIASES = {
     "base": "bert-base-cased", "large": "bert-large-cased", "tiny": "bert-tiny",
@@ -149,6 +173,7 @@ ALIASES = {
     "openai-community/gpt2-medium": "gpt2-medium",
     "llama-160m": "JackFram/llama-160m", "sheared-llama-1.3b": "princeton-nlp/Sheared-LLaMA-1.3B",
     "llama-2-7b": "meta-llama/Llama-2-7b-hf",
+    "tinyllama-1.1b": "TinyLlama/TinyLlama_v1.1", "llama-3-8b": "meta-llama/Meta-Llama-3-8B",
 }
 
 

@@ -1,4 +1,5 @@
-"""Llama-family decoder layer (HF ``LlamaDecoderLayer``, multi-head attention) and HF weight conversion.
+"""Llama-family decoder layer (HF ``LlamaDecoderLayer``, multi-head or grouped-query attention) and HF
+weight conversion.
 
     a_in = RMS1(x);  qkv = a_in qkv_w^T;  rotary(q, k);  ctx = causal attention;  o = ctx o_w^T
     z1 = x + o;  f_in = RMS2(z1);  gu = f_in gu_w^T;  a = silu(gate) * up;  out = z1 + a down_w^T
@@ -14,11 +15,17 @@ Two interchangeable implementations, as ``TransformerLayer``:
   weight and input gradients.
 * ``reference``: the same math in plain differentiable PyTorch.
 
-Weight layout: ``qkv_w [3h, h]`` is HF's q_proj, k_proj, v_proj rows concatenated, ``gu_w [2f, h]`` its
-gate_proj then up_proj rows, so HF checkpoints convert by ``torch.cat`` (``from_hf_state_dict`` /
-``to_hf_state_dict``; they only rename, concatenate and split -- nothing here reaches a hub).
+Weight layout: ``qkv_w [(H + 2 Hkv) D, h]`` (``[3h, h]`` for multi-head attention) is HF's q_proj, k_proj,
+v_proj rows concatenated, ``gu_w [2f, h]`` its gate_proj then up_proj rows, so HF checkpoints convert by
+``torch.cat`` (``from_hf_state_dict`` / ``to_hf_state_dict``; they only rename, concatenate and split --
+nothing here reaches a hub).
 
-Grouped-query attention, rotary scaling and a KV cache are not implemented.
+Grouped-query attention (``cfg.num_kv_heads`` = Hkv < H = ``cfg.num_heads``): the k and v projections have
+Hkv heads and query head i reads key/value head i // (H / Hkv) (HF's ``repeat_kv``).  The fused path never
+expands K / V: the rotary kernel rotates the H + Hkv heads of the q and k blocks and the attention kernels
+address K / V by group (ops/attention.py, ``kv_heads``).
+
+Rotary scaling, a sliding window and a KV cache are not implemented.
 """
 from __future__ import annotations
 
@@ -67,7 +74,8 @@ class LlamaLayer(nn.Module):
             raise ValueError("LlamaLayer needs norm='rms', rope_theta > 0 and activation='swiglu'")
         h, f = cfg.hidden_size, cfg.ffn_size
         self.cfg, self.rt = cfg, rt
-        self.qkv_w = nn.Parameter(torch.empty(3 * h, h))      # q rows, then k, then v
+        # q rows, then k, then v: [3h, h], or [(H + 2 Hkv) D, h] with grouped-query attention
+        self.qkv_w = nn.Parameter(torch.empty((cfg.num_heads + 2 * cfg.kv_heads) * cfg.head_dim, h))
         self.o_w = nn.Parameter(torch.empty(h, h))
         self.n1_g = nn.Parameter(torch.ones(h))               # input_layernorm
         self.gu_w = nn.Parameter(torch.empty(2 * f, h))       # gate rows, then up
@@ -119,10 +127,17 @@ class LlamaLayer(nn.Module):
         else:
             cs = table[position_ids.to(device=x.device, dtype=torch.int64).clamp(0, table.shape[0] - 1)]
         a_in = ref_rms_norm(x, self.n1_g, c.ln_eps)
-        qkv = F.linear(a_in, self.qkv_w).view(B, S, 3, H, D)
-        q = _ref_rope(qkv[:, :, 0], cs).transpose(1, 2)
-        k = _ref_rope(qkv[:, :, 1], cs).transpose(1, 2)
-        v = qkv[:, :, 2].transpose(1, 2)
+        Hkv = c.kv_heads
+        if Hkv == H:
+            qkv = F.linear(a_in, self.qkv_w).view(B, S, 3, H, D)
+            q = _ref_rope(qkv[:, :, 0], cs).transpose(1, 2)
+            k = _ref_rope(qkv[:, :, 1], cs).transpose(1, 2)
+            v = qkv[:, :, 2].transpose(1, 2)
+        else:    # grouped-query: K / V expanded to the query heads (HF repeat_kv)
+            qkv = F.linear(a_in, self.qkv_w).view(B, S, H + 2 * Hkv, D)
+            q = _ref_rope(qkv[:, :, :H], cs).transpose(1, 2)
+            k = _ref_rope(qkv[:, :, H:H + Hkv], cs).transpose(1, 2).repeat_interleave(H // Hkv, 1)
+            v = qkv[:, :, H + Hkv:].transpose(1, 2).repeat_interleave(H // Hkv, 1)
         s = torch.matmul(q, k.transpose(-1, -2)) * (1.0 / math.sqrt(D))
         if c.causal:
             s = s.masked_fill(torch.ones(S, S, dtype=torch.bool, device=s.device).triu(1), float("-inf"))
@@ -158,6 +173,7 @@ class _FusedLlamaLayerFn(torch.autograd.Function):
         (qkv_w, o_w, g1, gu_w, down_w, g2) = params
         B, S, h = x.shape
         H, D = c.num_heads, c.head_dim
+        Hkv = c.kv_heads if c.kv_heads != H else None      # None: the multi-head kernels and layout
         T = B * S
         p_a = c.attn_dropout if layer.training else 0.0
         rng = rt.rng
@@ -166,9 +182,9 @@ class _FusedLlamaLayerFn(torch.autograd.Function):
         eps = c.ln_eps
         _, a_in, r1 = Fx.rms_fwd(None, x2d, g1, eps)
         qkv = _linear(a_in, qkv_w)
-        Fx.rope_(qkv, table, B, S, H, D, pos=position_ids)     # in place: the rotated qkv is what is kept
+        Fx.rope_(qkv, table, B, S, H, D, pos=position_ids, kv_heads=Hkv)   # in place: the rotated qkv is what is kept
         actx, lse, amask = A.attn_fwd(qkv, B, S, H, D, c.causal, None, p_a, rng, sa,
-                                      key_range=key_range, doc_range=doc_range)
+                                      key_range=key_range, doc_range=doc_range, kv_heads=Hkv)
         o = _linear(actx, o_w)
         z1, f_in, r2 = Fx.rms_fwd(o, x2d, g2, eps)             # z1 = x + o and RMS2(z1) in one pass
         gu = _linear(f_in, gu_w)
@@ -181,6 +197,7 @@ class _FusedLlamaLayerFn(torch.autograd.Function):
         ctx.key_range, ctx.doc_range, ctx.position_ids, ctx.table = key_range, doc_range, position_ids, table
         ctx.rng = rng
         ctx.meta = (B, S, h, H, D, p_a, sa)
+        ctx.kv_heads = Hkv
         return out.view(B, S, h)
 
     @staticmethod
@@ -213,9 +230,9 @@ class _FusedLlamaLayerFn(torch.autograd.Function):
         emit_wgrad(o_w, dz1, actx, async_ok=True)
         dctx = _dgrad(dz1, o_w)
         dqkv = A.attn_bwd(dctx, qkv, actx, lse, B, S, H, D, c.causal, None, p_a, rng, sa, ctx.amask,
-                          key_range=ctx.key_range, doc_range=ctx.doc_range)
+                          key_range=ctx.key_range, doc_range=ctx.doc_range, kv_heads=ctx.kv_heads)
         # the rotation's adjoint is its inverse: dqkv back in front of the rotary embedding
-        Fx.rope_(dqkv, ctx.table, B, S, H, D, pos=ctx.position_ids, inverse=True)
+        Fx.rope_(dqkv, ctx.table, B, S, H, D, pos=ctx.position_ids, inverse=True, kv_heads=ctx.kv_heads)
         emit_wgrad(qkv_w, dqkv, a_in, async_ok=True)
         dain = _dgrad(dqkv, qkv_w)
         dx = Fx.rms_bwd(dain, dz1, x2d, r1, g1, dgamma=grad_dst(g1))
@@ -229,8 +246,9 @@ _HF_LAYER = "model.layers.{i}."
 
 def from_hf_state_dict(sd: dict) -> dict:
     """HF ``LlamaForCausalLM`` state dict -> ``CausalLM`` (Llama family) state dict: keys renamed,
-    q/k/v and gate/up concatenated along the output rows.  ``rotary_emb.inv_freq`` buffers of older
-    checkpoints are dropped; a tied checkpoint (no ``lm_head.weight``) gets the embedding table."""
+    q/k/v and gate/up concatenated along the output rows -- a grouped-query checkpoint's k_proj / v_proj
+    simply have fewer rows.  ``rotary_emb.inv_freq`` buffers of older checkpoints are dropped; a tied
+    checkpoint (no ``lm_head.weight``) gets the embedding table."""
     out = {"embeddings.word": sd["model.embed_tokens.weight"],
            "final_ln.weight": sd["model.norm.weight"],
            "head.own_weight": sd["lm_head.weight"] if "lm_head.weight" in sd else sd["model.embed_tokens.weight"]}
@@ -244,8 +262,9 @@ def from_hf_state_dict(sd: dict) -> dict:
         out[q + "gu_w"] = torch.cat([sd[mlp + "gate_proj.weight"], sd[mlp + "up_proj.weight"]], 0)
         out[q + "down_w"] = sd[mlp + "down_proj.weight"]
         out[q + "n2_g"] = sd[p + "post_attention_layernorm.weight"]
-        if out[q + "qkv_w"].shape[0] != 3 * out[q + "o_w"].shape[0]:
-            raise ValueError("grouped-query checkpoints (fewer key/value heads than query heads) are not supported")
+        if sd[att + "q_proj.weight"].shape[0] != out[q + "o_w"].shape[0] \
+                or sd[att + "k_proj.weight"].shape[0] != sd[att + "v_proj.weight"].shape[0]:
+            raise ValueError("q_proj must have as many rows as o_proj, and k_proj as many as v_proj")
         i += 1
     if i == 0:
         raise ValueError("not a Llama state dict: no model.layers.0.input_layernorm.weight")
@@ -253,14 +272,18 @@ def from_hf_state_dict(sd: dict) -> dict:
 
 
 def to_hf_state_dict(sd: dict) -> dict:
-    """The inverse of ``from_hf_state_dict``: split qkv_w into q/k/v and gu_w into gate/up."""
+    """The inverse of ``from_hf_state_dict``: split qkv_w into q/k/v and gu_w into gate/up.  The split
+    goes by sizes, so no config is needed: the q rows are as many as ``o_w``'s, the rest halves into k
+    and v (fewer rows than q with grouped-query attention)."""
     out = {"model.embed_tokens.weight": sd["embeddings.word"], "model.norm.weight": sd["final_ln.weight"],
            "lm_head.weight": sd["head.own_weight"]}
     i = 0
     while f"layers.{i}.qkv_w" in sd:
         p, q = _HF_LAYER.format(i=i), f"layers.{i}."
         att, mlp = p + "self_attn.", p + "mlp."
-        qw, kw, vw = sd[q + "qkv_w"].chunk(3, 0)
+        nq = sd[q + "o_w"].shape[0]
+        nkv = (sd[q + "qkv_w"].shape[0] - nq) // 2
+        qw, kw, vw = sd[q + "qkv_w"].split([nq, nkv, nkv], 0)
         gw, uw = sd[q + "gu_w"].chunk(2, 0)
         out[att + "q_proj.weight"], out[att + "k_proj.weight"], out[att + "v_proj.weight"] = qw, kw, vw
         out[att + "o_proj.weight"] = sd[q + "o_w"]

@@ -42,6 +42,7 @@ _SIGS = {
     "dtd_rms_bwd": (I, [I, P, P, P, P, P, P, P, P, I, I, P]),
     # rope.hip
     "dtd_rope": (I, [I, P, P, P, I, I, I, I, L, I, I, P]),
+    "dtd_rope_heads": (I, [I, P, P, P, I, I, I, I, L, I, I, P]),
     # swiglu.hip
     "dtd_swiglu_fwd": (I, [I, P, P, I, I, P]),
     "dtd_swiglu_bwd": (I, [I, P, P, P, P, I, I, P]),
@@ -90,6 +91,10 @@ _SIGS = {
     # document spans followed by the [B][ceil(S/128)][2] block bounds -- before the stream)
     "dtd_attn_fwd_doc": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, F, P, U32, P, P]),
     "dtd_attn_bwd_doc": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, F, P, P, P]),
+    # (the _gqa forms, Hkv < H key/value heads: q, k, v, o, lse | q, k, v, o, dout, lse, delta, dq, dk, dv;
+    # then B, S, H, Hkv, D, ld, ldo, causal, scale, the key ranges or null, the doc array or null)
+    "dtd_attn_fwd_gqa": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, F, P, P, P]),
+    "dtd_attn_bwd_gqa": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, F, P, P, P]),
     "dtd_attn_masks": (I, [P, I, I, I, F, P, U32, P]),
     "dtd_attn_set_bwd_form": (I, [I]),
     "dtd_attn_set_bwd_kernels": (I, [I]),

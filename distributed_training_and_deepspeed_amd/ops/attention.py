@@ -22,6 +22,15 @@ excludes: padding is an empty span here): the mask comes before ALiBi, whose bia
 absolute key position, the keep bits stay absolutely indexed, and a row without a key -- a pad -- has
 ctx = 0, lse = -inf, dq = 0 and contributes to no gradient; pad keys get dk = dv = 0.
 
+Grouped-query attention: ``kv_heads = Hkv`` (``H % Hkv == 0``, G = H / Hkv) gives the key/value
+projections Hkv heads; query head h reads key/value head h // G (HF's ``repeat_kv`` order).  The
+packed projection output is then ``qkv [B*S, (H + 2*Hkv)*D]``: the q block (H*D columns), then k
+(Hkv*D), then v (Hkv*D); ``dqkv`` has the same layout, its dK / dV the sums over each group's query
+heads (formed in fp32 inside the dK/dV kernel, rounded once).  ``ctx``, ``lse`` and ``delta`` stay
+per query head.  The causal mask, ``key_range`` and ``doc_range`` apply as above; dropout and ALiBi
+are not supported together with ``Hkv != H`` (``ValueError``).  ``kv_heads`` None or H is the
+multi-head layout above, on its own code paths.
+
 Reference semantics: HF BertSelfAttention eager path (matmul, softmax, dropout, matmul --
 SURVEY.md K2, reference model/transformer.py:80-86); the reference never passes an
 attention mask for BERT (data_parallel_training.py:53), so by default (no ``key_range``) padding
@@ -56,6 +65,34 @@ def alibi_slopes(num_heads: int) -> torch.Tensor:
 def _split(qkv, B, S, H, D):
     x = qkv.view(B, S, 3, H, D)
     return x[:, :, 0].transpose(1, 2), x[:, :, 1].transpose(1, 2), x[:, :, 2].transpose(1, 2)
+
+
+def _kv_heads(kv_heads, H: int) -> int:
+    """Hkv of a call: ``kv_heads`` (None = H), which must divide H."""
+    Hkv = H if kv_heads is None else int(kv_heads)
+    if Hkv <= 0 or H % Hkv:
+        raise ValueError(f"kv_heads = {Hkv} must be positive and divide the {H} query heads")
+    return Hkv
+
+
+def _check_gqa(qkv, B, S, H, Hkv, D, p, slopes):
+    """The grouped-query layout and what it excludes (module docstring)."""
+    if p > 0 or slopes is not None:
+        raise ValueError("grouped-query attention (kv_heads != H) supports neither dropout nor ALiBi")
+    if qkv.numel() != B * S * (H + 2 * Hkv) * D:
+        raise ValueError(f"qkv must be [B*S, (H + 2*Hkv)*D] = [{B * S}, {(H + 2 * Hkv) * D}], got {tuple(qkv.shape)}")
+
+
+def _split_gqa(qkv, B, S, H, Hkv, D):
+    """q [B, H, S, D] and the k, v [B, Hkv, S, D] of a grouped-query qkv."""
+    x = qkv.reshape(B, S, H + 2 * Hkv, D)
+    return (x[:, :, :H].transpose(1, 2), x[:, :, H:H + Hkv].transpose(1, 2), x[:, :, H + Hkv:].transpose(1, 2))
+
+
+def _gqa_entry(name: str) -> str:
+    if not _lib.has(name):
+        raise _lib.KernelError("the kernel library has no grouped-query attention entry points (stale build)")
+    return name
 
 
 def _cdt(t: torch.Tensor) -> torch.dtype:
@@ -217,9 +254,15 @@ def _drop_mask(B, H, S, p, rng, sid, device):
 
 
 def attn_fwd_ref(qkv, B, S, H, D, causal=False, slopes=None, p=0.0, rng: RngState | None = None, sid=0,
-                 scale=None, key_range=None, doc_range=None):
+                 scale=None, key_range=None, doc_range=None, kv_heads: int | None = None):
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
-    q, k, v = _split(qkv, B, S, H, D)
+    Hkv = _kv_heads(kv_heads, H)
+    if Hkv != H:     # K / V expanded to the H query heads (repeat_kv order)
+        _check_gqa(qkv, B, S, H, Hkv, D, p, slopes)
+        q, k, v = _split_gqa(qkv, B, S, H, Hkv, D)
+        k, v = k.repeat_interleave(H // Hkv, 1), v.repeat_interleave(H // Hkv, 1)
+    else:
+        q, k, v = _split(qkv, B, S, H, D)
     s = _scores(q, k, scale, causal, slopes, key_range, doc_range)
     lse = torch.logsumexp(s, -1)       # -inf for a row without a key
     prob = _probs(s, lse)
@@ -230,9 +273,15 @@ def attn_fwd_ref(qkv, B, S, H, D, causal=False, slopes=None, p=0.0, rng: RngStat
 
 
 def attn_bwd_ref(dctx, qkv, ctx, lse, B, S, H, D, causal=False, slopes=None, p=0.0, rng=None, sid=0, scale=None,
-                 key_range=None, doc_range=None):
+                 key_range=None, doc_range=None, kv_heads: int | None = None):
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
-    q, k, v = _split(qkv, B, S, H, D)
+    Hkv = _kv_heads(kv_heads, H)
+    if Hkv != H:
+        _check_gqa(qkv, B, S, H, Hkv, D, p, slopes)
+        q, k, v = _split_gqa(qkv, B, S, H, Hkv, D)
+        k, v = k.repeat_interleave(H // Hkv, 1), v.repeat_interleave(H // Hkv, 1)
+    else:
+        q, k, v = _split(qkv, B, S, H, D)
     s = _scores(q, k, scale, causal, slopes, key_range, doc_range)
     prob = _probs(s, lse)
     c = s.dtype
@@ -250,6 +299,10 @@ def attn_bwd_ref(dctx, qkv, ctx, lse, B, S, H, D, causal=False, slopes=None, p=0
     ds = prob * (dp - delta)
     dq = torch.matmul(ds, k.to(c)) * scale
     dk = torch.matmul(ds.transpose(-1, -2), q.to(c)) * scale
+    if Hkv != H:     # dK / dV: the sum over each group's query heads
+        dk, dv = (t.reshape(B, Hkv, H // Hkv, S, D).sum(2) for t in (dk, dv))
+        dqkv = torch.cat([dq, dk, dv], dim=1)   # [B, H + 2 Hkv, S, D]
+        return dqkv.permute(0, 2, 1, 3).reshape(B * S, (H + 2 * Hkv) * D).to(qkv.dtype)
     dqkv = torch.stack([dq, dk, dv], dim=2)  # [B,H,3,S,D]
     return dqkv.permute(0, 3, 2, 1, 4).reshape(B * S, 3 * H * D).to(qkv.dtype)
 
@@ -420,7 +473,7 @@ def attn_masks_async(B, S, H, D, p, rng: RngState, sid, device) -> PendingMasks 
 
 def attn_fwd(qkv, B, S, H, D, causal=False, slopes=None, p=0.0, rng: RngState | None = None, sid=0,
              masks: PendingMasks | None = None, key_range: torch.Tensor | None = None,
-             doc_range: DocRange | torch.Tensor | None = None):
+             doc_range: DocRange | torch.Tensor | None = None, kv_heads: int | None = None):
     """Returns (ctx [B*S, H*D], lse [B, H, S] fp32, masks).  ``masks`` holds the dropout keep
     bits for the backward ([2, B*H*S*ceil(S/32)] int32 on the kernel path, None otherwise);
     pass the ``attn_masks_async`` result to reuse masks generated ahead on a side stream.
@@ -431,8 +484,15 @@ def attn_fwd(qkv, B, S, H, D, causal=False, slopes=None, p=0.0, rng: RngState | 
 
     ``doc_range``: optional document spans of a packed batch (``DocRange``, or the bare int [B, S, 2]
     spans), exclusive with ``key_range``.  The bf16 kernels visit only the key tiles between each
-    128-query block's bounds; fp32 inputs take the math reference, as with a key range."""
+    128-query block's bounds; fp32 inputs take the math reference, as with a key range.
+
+    ``kv_heads``: grouped-query attention (module docstring): qkv is ``[B*S, (H + 2*Hkv)*D]``.  The
+    bf16 kernels read each query head's K/V tiles from its group's head; fp32 inputs take the math
+    reference.  None or H: the multi-head path, exactly as without the argument."""
     _exclusive(key_range, doc_range)
+    Hkv = _kv_heads(kv_heads, H)
+    if Hkv != H:
+        return _attn_fwd_gqa(qkv, B, S, H, Hkv, D, causal, slopes, p, key_range, doc_range)
     if (key_range is not None or doc_range is not None) and qkv.dtype == torch.float32:
         if masks is not None:    # keep bits generated ahead for the fp32 kernels: unused, but join
             torch.cuda.current_stream(qkv.device).wait_event(masks.event)   # before their buffer is freed
@@ -477,7 +537,7 @@ def attn_fwd(qkv, B, S, H, D, causal=False, slopes=None, p=0.0, rng: RngState | 
 
 def attn_bwd(dctx, qkv, ctx, lse, B, S, H, D, causal=False, slopes=None, p=0.0, rng=None, sid=0, masks=None,
              dbias=None, key_range: torch.Tensor | None = None,
-             doc_range: DocRange | torch.Tensor | None = None):
+             doc_range: DocRange | torch.Tensor | None = None, kv_heads: int | None = None):
     """Returns dqkv [B*S, 3*H*D] in the qkv layout.  ``dbias`` = (dst, acc): also writes the
     column sums of dqkv (the qkv projection's bias gradient) -- on the kernel path as per-wave
     partials from the dQ / dK,dV epilogues (no extra pass over dqkv).
@@ -487,9 +547,19 @@ def attn_bwd(dctx, qkv, ctx, lse, B, S, H, D, causal=False, slopes=None, p=0.0, 
     blocks outside the range.  fp32 inputs with a range take the math reference.
 
     ``doc_range``: the forward's document spans.  Pad keys get zero dK / dV and pad queries zero dQ;
-    the split kernels visit only the key tiles (dQ) / query tiles (dK/dV) between each block's bounds."""
+    the split kernels visit only the key tiles (dQ) / query tiles (dK/dV) between each block's bounds.
+
+    ``kv_heads``: the forward's (grouped-query attention): dqkv is ``[B*S, (H + 2*Hkv)*D]``; one
+    dK/dV workgroup per (key block, key/value head) sums its group's query heads in registers.
+    ``dbias`` then takes the column sums in a pass of its own (``bias_grad``)."""
     from . import functional as Fx
     _exclusive(key_range, doc_range)
+    Hkv = _kv_heads(kv_heads, H)
+    if Hkv != H:
+        dqkv = _attn_bwd_gqa(dctx, qkv, ctx, lse, B, S, H, Hkv, D, causal, slopes, p, key_range, doc_range)
+        if dbias is not None:
+            Fx.bias_grad(dqkv, *dbias)
+        return dqkv
     if (key_range is not None or doc_range is not None) and qkv.dtype == torch.float32:
         dqkv = attn_bwd_ref(dctx, qkv, ctx, lse, B, S, H, D, causal, slopes, p, rng, sid, key_range=key_range,
                             doc_range=doc_range)
@@ -535,6 +605,52 @@ def attn_bwd(dctx, qkv, ctx, lse, B, S, H, D, causal=False, slopes=None, p=0.0, 
             Fx._finalize(part, part.shape[0], ld, (dst, acc), acc)
         else:
             Fx.bias_grad(dqkv, *dbias)
+    return dqkv
+
+
+def _gqa_ranges(key_range, doc_range, B, S, device):
+    """(key-range pointer, doc pointer, the tensors kept alive) of a grouped-query kernel call."""
+    kr = _range_arg(key_range, B, device) if key_range is not None else None
+    doc = _doc_arg(doc_range, B, S, device) if doc_range is not None else None
+    return _lib.ptr(kr), _lib.ptr(doc), (kr, doc)
+
+
+def _attn_fwd_gqa(qkv, B, S, H, Hkv, D, causal, slopes, p, key_range, doc_range):
+    _check_gqa(qkv, B, S, H, Hkv, D, p, slopes)
+    if not kernel_supported(qkv, D):
+        if qkv.is_cuda and qkv.dtype == torch.bfloat16 and D in (64, 128):
+            _gqa_entry("dtd_attn_fwd_gqa")     # a GPU without the kernels is an error, not a fallback
+        ctx, lse = attn_fwd_ref(qkv, B, S, H, D, causal, key_range=key_range, doc_range=doc_range, kv_heads=Hkv)
+        return ctx, lse, None
+    name = _gqa_entry("dtd_attn_fwd_gqa")
+    qkv = qkv.contiguous()
+    ctx = torch.empty((B * S, H * D), dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty((B, H, S), dtype=torch.float32, device=qkv.device)
+    ld, es, base = (H + 2 * Hkv) * D, qkv.element_size(), qkv.data_ptr()
+    krp, docp, _keep = _gqa_ranges(key_range, doc_range, B, S, qkv.device)
+    _lib.call(name, base, base + H * D * es, base + (H + Hkv) * D * es, ctx.data_ptr(), lse.data_ptr(), B, S, H, Hkv,
+              D, ld, H * D, int(causal), 1.0 / math.sqrt(D), krp, docp, _lib.stream())
+    return ctx, lse, None
+
+
+def _attn_bwd_gqa(dctx, qkv, ctx, lse, B, S, H, Hkv, D, causal, slopes, p, key_range, doc_range):
+    _check_gqa(qkv, B, S, H, Hkv, D, p, slopes)
+    if not kernel_supported(qkv, D):
+        if qkv.is_cuda and qkv.dtype == torch.bfloat16 and D in (64, 128):
+            _gqa_entry("dtd_attn_bwd_gqa")
+        return attn_bwd_ref(dctx, qkv, ctx, lse, B, S, H, D, causal, key_range=key_range, doc_range=doc_range,
+                            kv_heads=Hkv)
+    name = _gqa_entry("dtd_attn_bwd_gqa")
+    dctx = dctx.contiguous()
+    dqkv = torch.empty_like(qkv)
+    delta = torch.empty((B, H, S), dtype=torch.float32, device=qkv.device)
+    ld, es = (H + 2 * Hkv) * D, qkv.element_size()
+    qb, gb = qkv.data_ptr(), dqkv.data_ptr()
+    ko, vo = H * D * es, (H + Hkv) * D * es
+    krp, docp, _keep = _gqa_ranges(key_range, doc_range, B, S, qkv.device)
+    _lib.call(name, qb, qb + ko, qb + vo, ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr(), delta.data_ptr(),
+              gb, gb + ko, gb + vo, B, S, H, Hkv, D, ld, H * D, int(causal), 1.0 / math.sqrt(D), krp, docp,
+              _lib.stream())
     return dqkv
 
 

@@ -35,6 +35,13 @@
 // the documents of a row, and each workgroup visits only the tiles between its block's bounds -- the
 // DOC instantiations, reached through dtd_attn_fwd_doc / dtd_attn_bwd_doc only).  q/k/v/o are strided views (row stride `ld`) into the
 // fused [B*S, 3*H*D] projection output, so no transpose/copy kernels are needed.
+//
+// Grouped-query attention (Hkv < H key/value heads, G = H / Hkv; query head h reads key/value head
+// h / G): the projection output is [B*S, (H + 2*Hkv)*D] -- q block, then k, then v -- and the same
+// three strided views address it; only the head offset of K, V, dK and dV changes.  The *_gqa_kernel
+// forms (dtd_attn_fwd_gqa / dtd_attn_bwd_gqa only; no dropout, no ALiBi) keep the forward's and dQ's
+// grid and read their K/V tiles from head h / G; dK/dV runs on grid (ceil(S/128), B*Hkv) and sums
+// its group's G query heads in the accumulators.  ctx, lse and delta stay per query head.
 #include <stdio.h>
 #include <type_traits>
 #include <stdlib.h>
@@ -185,7 +192,8 @@ struct FwdArgs {
   // block -- and with it the other instantiations' register figures -- stays as it was: [B][S][2] =
   // half-open span (lo, hi) of each position's document ((0, 0) for a pad), followed at once by
   // [B][ceil(S/128)][2] = (min lo, max hi) over each 128-position block's non-empty rows ((0, 0) for
-  // a block without one).
+  // a block without one).  // GQA kernels (no dropout, so no keep words) likewise read Hkv, the number of key/value heads,
+  // from W -- here and in BwdArgs.
 };
 
 // Key range of sequence b, clamped to [0, S]; b is workgroup-uniform, so both are scalar loads and
@@ -502,12 +510,20 @@ struct TileLoader {
 // so that the instantiations without it keep their symbols; both include attention_fwd_body.h.
 template <int D, int OCC, int BN, int RING, bool PK = false, bool RANGE = false>
 __global__ void __launch_bounds__(256, OCC) attn_fwd_kernel(FwdArgs a) {
-  constexpr bool DOC = false;
+  constexpr bool DOC = false, GQA = false;
 #include "attention_fwd_body.h"
 }
 template <int D, int OCC, int BN, int RING>
 __global__ void __launch_bounds__(256, OCC) attn_fwd_doc_kernel(FwdArgs a) {
-  constexpr bool PK = false, RANGE = false, DOC = true;
+  constexpr bool PK = false, RANGE = false, DOC = true, GQA = false;
+#include "attention_fwd_body.h"
+}
+// Grouped-query form (Hkv < H key/value heads, query head h reads key/value head h / (H / Hkv)): a
+// kernel of its own name again.  MODE 0: plain, 1: key range, 2: document spans.  No dropout, no
+// ALiBi; the argument block is FwdArgs as it stands, with Hkv in the (then unused) field W.
+template <int D, int OCC, int BN, int RING, int MODE>
+__global__ void __launch_bounds__(256, OCC) attn_fwd_gqa_kernel(FwdArgs a) {
+  constexpr bool PK = false, RANGE = MODE == 1, DOC = MODE == 2, GQA = true;
 #include "attention_fwd_body.h"
 }
 
@@ -756,12 +772,22 @@ __device__ __forceinline__ int colsum_col(int k, int hh) { return (k >> 4) * 32 
 // below.)
 template <int D, int OCC, int BM, bool DROP, bool ALIBI, bool MASK = true, bool RANGE = false>
 __global__ void __launch_bounds__(256, OCC) attn_bwd_dkdv_kernel(BwdArgs a) {
-  constexpr bool DOC = false;
+  constexpr bool DOC = false, GQA = false;
 #include "attention_bwd_dkdv_body.h"
 }
 template <int D, int OCC, int BM, bool DROP, bool ALIBI>
 __global__ void __launch_bounds__(256, OCC) attn_bwd_dkdv_doc_kernel(BwdArgs a) {
-  constexpr bool MASK = true, RANGE = false, DOC = true;
+  constexpr bool MASK = true, RANGE = false, DOC = true, GQA = false;
+#include "attention_bwd_dkdv_body.h"
+}
+// Grouped-query form: grid (ceil(S/128), B * Hkv).  A workgroup keeps its 128 keys' K/V fragments
+// and the dK/dV accumulators once and walks the query tiles of the G = H / Hkv query heads of its
+// group as one tile sequence, so the group's sum is formed in the fp32 accumulators in a fixed
+// order and rounded once (no atomics, no partial buffers).  Always the masked form; MODE as in
+// attn_fwd_gqa_kernel; Hkv in BwdArgs::W.
+template <int D, int OCC, int BM, int MODE>
+__global__ void __launch_bounds__(256, OCC) attn_bwd_dkdv_gqa_kernel(BwdArgs a) {
+  constexpr bool DROP = false, ALIBI = false, MASK = true, RANGE = MODE == 1, DOC = MODE == 2, GQA = true;
 #include "attention_bwd_dkdv_body.h"
 }
 
@@ -775,12 +801,17 @@ __global__ void __launch_bounds__(256, OCC) attn_bwd_dkdv_doc_kernel(BwdArgs a) 
 // (attn_bwd_dq_doc_kernel, below).
 template <int D, int OCC, int BN, int RING, bool PK = false, bool RANGE = false>
 __global__ void __launch_bounds__(256, OCC) attn_bwd_dq_kernel(BwdArgs a) {
-  constexpr bool DOC = false;
+  constexpr bool DOC = false, GQA = false;
 #include "attention_bwd_dq_body.h"
 }
 template <int D, int OCC, int BN, int RING>
 __global__ void __launch_bounds__(256, OCC) attn_bwd_dq_doc_kernel(BwdArgs a) {
-  constexpr bool PK = false, RANGE = false, DOC = true;
+  constexpr bool PK = false, RANGE = false, DOC = true, GQA = false;
+#include "attention_bwd_dq_body.h"
+}
+template <int D, int OCC, int BN, int RING, int MODE>
+__global__ void __launch_bounds__(256, OCC) attn_bwd_dq_gqa_kernel(BwdArgs a) {
+  constexpr bool PK = false, RANGE = MODE == 1, DOC = MODE == 2, GQA = true;
 #include "attention_bwd_dq_body.h"
 }
 
@@ -1477,6 +1508,33 @@ DTD_EXPORT int dtd_attn_fwd_doc(const void* q, const void* k, const void* v, voi
                          doc, s);
 }
 
+// Grouped-query forward: Hkv < H key/value heads (H % Hkv == 0), k / v hold Hkv heads of D columns.
+// No dropout, no ALiBi.  kv_range / doc: at most one, as in attn_fwd_launch; the kernels take the
+// default tile forms of the multi-head kernels they derive from.
+template <int MODE>
+static void launch_fwd_gqa(int D, dim3 grid, hipStream_t s, const FwdArgs& a) {
+  if (D == 64) hipLaunchKernelGGL((attn_fwd_gqa_kernel<64, 3, 64, 1, MODE>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((attn_fwd_gqa_kernel<128, 1, 64, 2, MODE>), grid, dim3(256), 0, s, a);
+}
+DTD_EXPORT int dtd_attn_fwd_gqa(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H,
+                                int Hkv, int D, int ld, int ldo, int causal, float scale, const int* kv_range,
+                                const int* doc, hipStream_t s) {
+  if (B * S * H == 0) return 0;
+  if (Hkv <= 0 || Hkv >= H || H % Hkv) return (int)hipErrorInvalidValue;
+  if (kv_range && doc) return (int)hipErrorInvalidValue;
+  if (D != 64 && D != 128) return (int)hipErrorInvalidValue;
+  if (!offsets_fit(S, ld, ldo)) return (int)hipErrorInvalidValue;
+  const char* thr_env = getenv("DTD_ATTN_RESCALE_THR");
+  const float thr = thr_env ? (float)atof(thr_env) : kRescaleThr;
+  FwdArgs a{(const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, lse, nullptr, nullptr, nullptr, B, S, H, ld, ldo,
+            causal, /*W = */ Hkv, scale, 0.f, thr, doc ? doc : kv_range};
+  dim3 grid((S + 127) / 128, B * H);
+  if (doc) launch_fwd_gqa<2>(D, grid, s, a);
+  else if (kv_range) launch_fwd_gqa<1>(D, grid, s, a);
+  else launch_fwd_gqa<0>(D, grid, s, a);
+  DTD_LAUNCH_CHECK();
+}
+
 // 0 = the dQ + dK/dV pair, 1 = fused where it applies, 2 = fused, 4-wave form; returns the previous
 DTD_EXPORT int dtd_attn_fused_bwd_built() { return DTD_ATTN_FUSED_BWD; }
 
@@ -1628,6 +1686,38 @@ static int attn_bwd_launch(const void* q, const void* k, const void* v, const vo
     if (run_dq) hipLaunchKernelGGL((attn_bwd_dq_kernel<128, 1, 64, 2>), grid, dim3(256), 0, s, a);
     if (run_dkdv) launch_dkdv<128, 1, 64>(grid, s, a);
   }
+  DTD_LAUNCH_CHECK();
+}
+
+// Grouped-query backward (see dtd_attn_fwd_gqa): dq holds H heads, dk / dv Hkv heads.  dQ runs on
+// grid (ceil(S/128), B * H) and writes delta, dK/dV then on (ceil(S/128), B * Hkv).
+template <int MODE>
+static void launch_bwd_gqa(int D, dim3 gq, dim3 gkv, hipStream_t s, const BwdArgs& a) {
+  const bool run_dq = g_bwd_kernels & 1, run_dkdv = g_bwd_kernels & 2;
+  if (D == 64) {
+    if (run_dq) hipLaunchKernelGGL((attn_bwd_dq_gqa_kernel<64, 3, 64, 1, MODE>), gq, dim3(256), 0, s, a);
+    if (run_dkdv) hipLaunchKernelGGL((attn_bwd_dkdv_gqa_kernel<64, 2, 128, MODE>), gkv, dim3(256), 0, s, a);
+  } else {
+    if (run_dq) hipLaunchKernelGGL((attn_bwd_dq_gqa_kernel<128, 1, 64, 2, MODE>), gq, dim3(256), 0, s, a);
+    if (run_dkdv) hipLaunchKernelGGL((attn_bwd_dkdv_gqa_kernel<128, 1, 64, MODE>), gkv, dim3(256), 0, s, a);
+  }
+}
+DTD_EXPORT int dtd_attn_bwd_gqa(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                                const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int S, int H,
+                                int Hkv, int D, int ld, int ldo, int causal, float scale, const int* kv_range,
+                                const int* doc, hipStream_t s) {
+  if (B * S * H == 0) return 0;
+  if (Hkv <= 0 || Hkv >= H || H % Hkv) return (int)hipErrorInvalidValue;
+  if (kv_range && doc) return (int)hipErrorInvalidValue;
+  if (D != 64 && D != 128) return (int)hipErrorInvalidValue;
+  if (!offsets_fit(S, ld, ldo)) return (int)hipErrorInvalidValue;
+  BwdArgs a{(const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)dout, lse, delta, (const bf16*)o,
+            (bf16*)dq, (bf16*)dk, (bf16*)dv, nullptr, nullptr, nullptr, B, S, H, ld, ldo, causal, /*W = */ Hkv, scale,
+            0.f, nullptr, doc ? doc : kv_range};
+  const dim3 gq((S + 127) / 128, B * H), gkv((S + 127) / 128, B * Hkv);
+  if (doc) launch_bwd_gqa<2>(D, gq, gkv, s, a);
+  else if (kv_range) launch_bwd_gqa<1>(D, gq, gkv, s, a);
+  else launch_bwd_gqa<0>(D, gq, gkv, s, a);
   DTD_LAUNCH_CHECK();
 }
 

@@ -1,5 +1,5 @@
 // Body of attn_bwd_dkdv_kernel / attn_bwd_dkdv_doc_kernel (attention.hip), included inside both (see
-// attention_fwd_body.h).  Expects D, OCC, BM, DROP, ALIBI, MASK, RANGE, DOC and the argument `a`.
+// attention_fwd_body.h).  Expects D, OCC, BM, DROP, ALIBI, MASK, RANGE, DOC, GQA and the argument `a`.
   static_assert(MASK || !(RANGE || DOC), "a key range needs the masked form");
   static_assert(!(RANGE && DOC), "a key range and document spans are exclusive");
   constexpr bool SWZ = D == 64;                 // swizzled unpadded image (swz64_off)
@@ -22,7 +22,17 @@
   int tx, ty;
   if constexpr (RANGE || DOC) xcd_tile_grouped(tx, ty);
   else xcd_tile(tx, ty);
-  const int bh = ty, b = bh / a.H, h = bh % a.H;
+  // GQA: grid y = B * Hkv (Hkv rides in a.W: the GQA forms run without dropout).  The workgroup
+  // owns key/value head hk of sequence b and walks the query tiles of its G = H / Hkv query heads
+  // hk * G .. hk * G + G - 1 in turn; `h` / `bh` name the query head whose tile is being fetched.
+  int bh = ty, b = bh / a.H, h = bh % a.H, hk = h, G = 1;
+  if constexpr (GQA) {
+    b = ty / a.W;
+    hk = ty % a.W;
+    G = a.H / a.W;
+    h = hk * G;
+    bh = b * a.H + h;
+  }
   const int S = a.S;
   const int kblk = tx * 128;
   const int key = kblk + w * 32 + r;
@@ -34,14 +44,14 @@
     if constexpr (RANGE) load_range(a.kv_range, b, S, klo, khi);
     // block-uniform: no key of this block is in the range (DOC: every key of it is a pad)
     if (DOC ? klo >= khi : (kblk >= khi || kblk + 128 <= klo)) {
-      if (a.bias_part && D == 64) {
+      if (!GQA && a.bias_part && D == 64) {
         float* row = a.bias_part + ((size_t)b * gridDim.x * 4 + (kblk >> 5) + w) * (3 * a.H * D) + h * D + colsum_col(r, hh);
         row[a.H * D] = 0.f;
         row[2 * a.H * D] = 0.f;
       }
       if (kvalid) {
-        bf16* dkp = a.dk + (size_t)(b * S + key) * a.ld + h * D;
-        bf16* dvp = a.dv + (size_t)(b * S + key) * a.ld + h * D;
+        bf16* dkp = a.dk + (size_t)(b * S + key) * a.ld + hk * D;
+        bf16* dvp = a.dv + (size_t)(b * S + key) * a.ld + hk * D;
 #pragma unroll
         for (int c = 0; c < D / 16; ++c) {   // both half-waves hold lane r's key: 8 of 16 columns each
           *reinterpret_cast<bf16x8*>(dkp + 16 * c + 8 * hh) = bf16x8{};
@@ -64,15 +74,15 @@
   const int Sp = 32 * a.W;
   const uint32_t* mrow = drop ? a.maskA + ((size_t)bh * a.W + min((kblk >> 5) + w, a.W - 1)) * Sp : nullptr;
   const __amdgpu_buffer_rsrc_t mrs = bounded_rsrc(drop ? (const void*)mrow : (const void*)a.lse, drop ? (uint32_t)Sp * 4u : 0u);
-  const RowSrc qsrc = row_src<D>(a.q + (size_t)b * S * a.ld + h * D, a.ld, S);
-  const RowSrc osrc = row_src<D>(a.dout + (size_t)b * S * a.ldo + h * D, a.ldo, S);
+  RowSrc qsrc = row_src<D>(a.q + (size_t)b * S * a.ld + h * D, a.ld, S);
+  RowSrc osrc = row_src<D>(a.dout + (size_t)b * S * a.ldo + h * D, a.ldo, S);
   // row statistics of one (batch, head): bounded resources over the [S] rows, so rows past S read 0
-  const __amdgpu_buffer_rsrc_t lse_rs = bounded_rsrc(a.lse + (size_t)bh * S, (uint32_t)S * 4u);
-  const __amdgpu_buffer_rsrc_t del_rs = bounded_rsrc(a.delta + (size_t)bh * S, (uint32_t)S * 4u);
+  __amdgpu_buffer_rsrc_t lse_rs = bounded_rsrc(a.lse + (size_t)bh * S, (uint32_t)S * 4u);
+  __amdgpu_buffer_rsrc_t del_rs = bounded_rsrc(a.delta + (size_t)bh * S, (uint32_t)S * 4u);
 
   bf16x8 kf[NC], vf[NC];
-  load_frags<D>(kf, a.k + (size_t)b * S * a.ld + h * D, a.ld, S, key, hh);   // keys past S: 0
-  load_frags<D>(vf, a.v + (size_t)b * S * a.ld + h * D, a.ld, S, key, hh);
+  load_frags<D>(kf, a.k + (size_t)b * S * a.ld + hk * D, a.ld, S, key, hh);   // keys past S: 0
+  load_frags<D>(vf, a.v + (size_t)b * S * a.ld + hk * D, a.ld, S, key, hh);
   f32x16 dk[NDB], dv[NDB];
 #pragma unroll
   for (int d = 0; d < NDB; ++d) { dk[d] = f32x16{}; dv[d] = f32x16{}; }
@@ -124,12 +134,31 @@
   ol.store_bwd(Os[0], QP);
   store_stats(0, qstart);
   __syncthreads();
-  for (int t = 0; t < nt; ++t) {
-    const int buf = t & 1, q0 = qstart + t * BM;
-    if (t + 1 < nt) {
-      ql.load(qsrc, q0 + BM);
-      ol.load(osrc, q0 + BM);
-      load_stats(q0 + BM);
+  // GQA: the G heads' tile sequences run as one, nt tiles each, into the same accumulators.  The
+  // sources are only read by the prefetch, so they are rebased (scalar registers) where the
+  // prefetch crosses a head seam: the last tile of a head fetches the next head's first tile, and
+  // the double buffer never drains.  tq = the tile being fetched, inside its head.
+  const int ntot = GQA ? nt * G : nt;
+  int tq = 0, qseam = 0;   // (GQA only) qseam: the tile fetched is the first of the next head
+  for (int t = 0; t < ntot; ++t) {
+    const int buf = t & 1, q0 = qstart + (GQA ? tq : t) * BM;
+    if (t + 1 < ntot) {
+      if constexpr (GQA) {
+        qseam = 0;
+        if (++tq == nt) {
+          tq = 0;
+          qseam = 1;
+          ++h;
+          bh = b * a.H + h;
+          qsrc.rs = row_src<D>(a.q + (size_t)b * S * a.ld + h * D, a.ld, S).rs;   // (voff, ld2 stay)
+          osrc.rs = row_src<D>(a.dout + (size_t)b * S * a.ldo + h * D, a.ldo, S).rs;
+          lse_rs = bounded_rsrc(a.lse + (size_t)bh * S, (uint32_t)S * 4u);
+          del_rs = bounded_rsrc(a.delta + (size_t)bh * S, (uint32_t)S * 4u);
+        }
+      }
+      ql.load(qsrc, GQA && qseam ? qstart : q0 + BM);
+      ol.load(osrc, GQA && qseam ? qstart : q0 + BM);
+      load_stats(GQA && qseam ? qstart : q0 + BM);
       if (drop) prefetch_words(q0 + BM);
     }
     const bf16* Q = Qs[buf];
@@ -227,16 +256,16 @@
         }
       }
     }
-    if (t + 1 < nt) {
+    if (t + 1 < ntot) {
       ql.store_bwd(Qs[buf ^ 1], QP);
       ol.store_bwd(Os[buf ^ 1], QP);
-      store_stats(buf ^ 1, q0 + BM);
+      store_stats(buf ^ 1, GQA && qseam ? qstart : q0 + BM);
     }
     __syncthreads();
   }
   const float dv_scale = inv_keep;   // the dropped P fed to dV carried keep bits only
   const float dk_scale = a.scale * inv_keep;   // dS' = (1 - p) dS (see load_stats)
-  if (a.bias_part && D == 64) {
+  if (!GQA && a.bias_part && D == 64) {
     float vk[32], vv[32];
 #pragma unroll
     for (int d = 0; d < NDB; ++d)
@@ -250,5 +279,5 @@
     row[a.H * D] = sk;
     row[2 * a.H * D] = sv;
   }
-  store_rows16<NDB>(a.dk + (size_t)(b * S + key) * a.ld + h * D, dk, dk_scale, hh, kvalid);
-  store_rows16<NDB>(a.dv + (size_t)(b * S + key) * a.ld + h * D, dv, dv_scale, hh, kvalid);
+  store_rows16<NDB>(a.dk + (size_t)(b * S + key) * a.ld + hk * D, dk, dk_scale, hh, kvalid);
+  store_rows16<NDB>(a.dv + (size_t)(b * S + key) * a.ld + hk * D, dv, dv_scale, hh, kvalid);

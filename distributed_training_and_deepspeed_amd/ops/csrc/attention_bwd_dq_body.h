@@ -1,5 +1,5 @@
 // Body of attn_bwd_dq_kernel / attn_bwd_dq_doc_kernel (attention.hip), included inside both (see
-// attention_fwd_body.h).  Expects D, OCC, BN, RING, PK, RANGE, DOC and the argument `a`.
+// attention_fwd_body.h).  Expects D, OCC, BN, RING, PK, RANGE, DOC, GQA and the argument `a`.
   static_assert(!(RANGE && DOC), "a key range and document spans are exclusive");
   constexpr bool RNG = RANGE || DOC;
   constexpr bool SWZ = D == 64;                 // swizzled unpadded K / V images (swz64_off)
@@ -16,12 +16,14 @@
   const int qblk = tx * 128, q0 = qblk + w * 32;
   const int q = q0 + r;
   const bool qvalid = q < S;
+  int hk = h;   // GQA: the key/value head h / G (Hkv rides in a.W, see attention_fwd_body.h)
+  if constexpr (GQA) hk = __builtin_amdgcn_readfirstlane(h / (a.H / a.W));
   const float sl2 = a.slopes ? a.slopes[h] * kLog2e : 0.f;
   const float sc2 = a.scale * kLog2e;
   const bool drop = a.maskA != nullptr;
   const float inv_keep = drop ? 1.f / (1.f - a.p) : 1.f;
-  const RowSrc ksrc = row_src<D>(a.k + (size_t)b * S * a.ld + h * D, a.ld, S);
-  const RowSrc vsrc = row_src<D>(a.v + (size_t)b * S * a.ld + h * D, a.ld, S);
+  const RowSrc ksrc = row_src<D>(a.k + (size_t)b * S * a.ld + hk * D, a.ld, S);
+  const RowSrc vsrc = row_src<D>(a.v + (size_t)b * S * a.ld + hk * D, a.ld, S);
   // keep masks as in attn_fwd_kernel: 64-bit lane masks of the key-major layout, scalar loads
   const int Sp = 32 * a.W;
   const uint32_t* mrow = drop ? a.maskB + ((size_t)bh * a.W + min(q0 >> 5, a.W - 1)) * Sp : nullptr;
@@ -196,7 +198,7 @@
     tile(std::integral_constant<int, 1>{}, t);
     if (t + 1 < nt) tile(std::integral_constant<int, 0>{}, t + 1);
   }
-  if (a.bias_part && D == 64) {
+  if (!GQA && a.bias_part && D == 64) {
     float vq[32];
 #pragma unroll
     for (int d = 0; d < NDB; ++d)

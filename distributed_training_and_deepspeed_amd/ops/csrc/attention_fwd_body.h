@@ -1,6 +1,6 @@
 // Body of attn_fwd_kernel / attn_fwd_doc_kernel (attention.hip), included inside both: a shared
 // __device__ function, inlined, did not leave the existing instantiations' registers as they were.
-// Expects the template parameters D, OCC, BN, RING and the constants PK, RANGE, DOC in scope, and
+// Expects the template parameters D, OCC, BN, RING and the constants PK, RANGE, DOC, GQA in scope, and
 // the kernel argument `a`.
   static_assert(!(RANGE && DOC), "a key range and document spans are exclusive");
   constexpr bool RNG = RANGE || DOC;            // a tile range [t0, nt) that need not start at 0
@@ -21,12 +21,16 @@
   const int qblk = tx * 128, q0 = qblk + w * 32;
   const int q = q0 + r;
   const bool qvalid = q < S;
+  // GQA: K/V come from head h / G (G = H / Hkv query heads per key/value head; the GQA forms run
+  // without dropout, so the argument block's keep-word count W carries Hkv); workgroup-uniform
+  int hk = h;
+  if constexpr (GQA) hk = __builtin_amdgcn_readfirstlane(h / (a.H / a.W));
   const float sl2 = a.slopes ? a.slopes[h] * kLog2e : 0.f;
   const float sc2 = a.scale * kLog2e;
   const bool drop = a.maskA != nullptr;
   const float inv_keep = drop ? 1.f / (1.f - a.p) : 1.f;
-  const RowSrc ksrc = row_src<D>(a.k + (size_t)b * S * a.ld + h * D, a.ld, S);
-  const RowSrc vsrc = row_src<D>(a.v + (size_t)b * S * a.ld + h * D, a.ld, S);
+  const RowSrc ksrc = row_src<D>(a.k + (size_t)b * S * a.ld + hk * D, a.ld, S);
+  const RowSrc vsrc = row_src<D>(a.v + (size_t)b * S * a.ld + hk * D, a.ld, S);
   // dropout: this wave's 32 queries are one query word of the key-major layout, so the keep masks
   // of a 32-key block are 16 aligned 64-bit words (lm_pos) -- scalar loads, one v_cndmask per
   // score.  A one-dword-per-lane vector load of the same 64 words a tile ahead pulls them into L2.

@@ -440,13 +440,20 @@ def rope_table(max_positions: int, head_dim: int, theta: float = 10000.0, device
 
 
 def rope_(qkv: torch.Tensor, table: torch.Tensor, B: int, S: int, H: int, D: int, pos: torch.Tensor | None = None,
-          inverse: bool = False) -> torch.Tensor:
+          inverse: bool = False, kv_heads: int | None = None) -> torch.Tensor:
     """Rotate the q and k slices of the packed ``qkv [B*S, 3*H*D]`` IN PLACE (HF's rotate-half
     convention; v untouched) and return it.  ``table``: ``rope_table`` on qkv's device.  ``pos``:
     optional integer [B, S] position per token (default s).  ``inverse`` negates the sine: the inverse
-    rotation, which is also the adjoint -- the backward is ``rope_(dqkv, ..., inverse=True)``."""
-    if qkv.dim() != 2 or qkv.shape[0] != B * S or qkv.shape[1] != 3 * H * D or qkv.stride(1) != 1:
-        raise ValueError(f"rope_: qkv must be [B*S, 3*H*D] = [{B * S}, {3 * H * D}], got {tuple(qkv.shape)}")
+    rotation, which is also the adjoint -- the backward is ``rope_(dqkv, ..., inverse=True)``.
+
+    ``kv_heads`` (grouped-query attention, ops/attention.py): qkv is ``[B*S, (H + 2*Hkv)*D]`` and the
+    H + Hkv heads of its q and k blocks are rotated."""
+    Hkv = H if kv_heads is None else int(kv_heads)
+    if Hkv <= 0 or H % Hkv:
+        raise ValueError(f"rope_: kv_heads = {Hkv} must divide the {H} query heads")
+    width, nrot = (H + 2 * Hkv) * D, H + Hkv
+    if qkv.dim() != 2 or qkv.shape[0] != B * S or qkv.shape[1] != width or qkv.stride(1) != 1:
+        raise ValueError(f"rope_: qkv must be [B*S, (H + 2*Hkv)*D] = [{B * S}, {width}], got {tuple(qkv.shape)}")
     if tuple(table.shape[1:]) != (D // 2, 2) or table.dtype != torch.float32 or table.device != qkv.device:
         raise ValueError("rope_: table must be rope_table(max_positions, D) (fp32 [P, D/2, 2]) on qkv's device")
     if pos is None and S > table.shape[0]:
@@ -457,6 +464,12 @@ def rope_(qkv: torch.Tensor, table: torch.Tensor, B: int, S: int, H: int, D: int
             and _lib.has("dtd_rope"):
         table = table.contiguous()
         p32 = pos.reshape(-1).to(device=qkv.device, dtype=torch.int32).contiguous() if pos is not None else None
+        if Hkv != H:
+            if not _lib.has("dtd_rope_heads"):
+                raise _lib.KernelError("the kernel library has no grouped-query rope entry point (stale build)")
+            _lib.call("dtd_rope_heads", _lib.dt(qkv), qkv.data_ptr(), table.data_ptr(), _lib.ptr(p32), B, S, nrot, D,
+                      qkv.stride(0), table.shape[0], int(inverse), _lib.stream())
+            return qkv
         _lib.call("dtd_rope", _lib.dt(qkv), qkv.data_ptr(), table.data_ptr(), _lib.ptr(p32), B, S, H, D,
                   qkv.stride(0), table.shape[0], int(inverse), _lib.stream())
         return qkv
@@ -468,10 +481,10 @@ def rope_(qkv: torch.Tensor, table: torch.Tensor, B: int, S: int, H: int, D: int
     c, s = cs[:, None, :, 0], cs[:, None, :, 1]
     if inverse:
         s = -s
-    x = qkv[:, :2 * H * D].reshape(B * S, 2 * H, D).float()
+    x = qkv[:, :nrot * D].reshape(B * S, nrot, D).float()
     x1, x2 = x[..., :D // 2], x[..., D // 2:]
     out = torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], -1)
-    qkv[:, :2 * H * D] = out.reshape(B * S, 2 * H * D).to(qkv.dtype)
+    qkv[:, :nrot * D] = out.reshape(B * S, nrot * D).to(qkv.dtype)
     return qkv
 
 

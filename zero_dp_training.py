@@ -18,7 +18,9 @@ values, quirk 12).
   torchrun --nproc-per-node 8 zero_dp_training.py --stage 2
   python zero_dp_training.py --num-gpus 2 --stage 3 --model-name facebook/opt-125m
   python zero_dp_training.py --stage 3 --model-name meta-llama/Llama-2-7b-hf      # Llama family (models/llama.py):
-                                   # also JackFram/llama-160m, princeton-nlp/Sheared-LLaMA-1.3B, llama-tiny
+                                   # also JackFram/llama-160m, princeton-nlp/Sheared-LLaMA-1.3B, llama-tiny, and with
+                                   # grouped-query attention TinyLlama/TinyLlama_v1.1, meta-llama/Meta-Llama-3-8B,
+                                   # llama-tiny-gqa
 """
 import argparse
 import json
