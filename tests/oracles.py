@@ -1,15 +1,18 @@
 """Float64 oracles, a per-slice error metric and named input regimes for the streaming kernels
 (LayerNorm, RMSNorm, row softmax, cross-entropy, activations, SwiGLU, RoPE, dropout-add, fused Adam,
-sq-norm, scale-cast).
+sq-norm, scale-cast) and for attention.
 
-A plain helper module: no fixtures, and nothing from the package but ``ops.rng.keep_mask`` (the
-dropout keep bits are an input of the oracles, not something they re-derive).  Every oracle takes
+A plain helper module: no fixtures, and nothing from the package but ``ops.rng.keep_mask`` and
+``ops.rng.attn_keep_mask`` (the dropout keep bits are an input of the oracles, not something they
+re-derive).  Every oracle takes
 the kernel's inputs in their storage dtype, upcasts them to fp64 (exact for bf16 and fp32), builds
 the forward from torch operators and takes every gradient with ``torch.autograd.grad`` -- no
 hand-derived backward formulas, so a formula error in a kernel and in the CPU branch of
-``ops/functional.py`` cannot hide in the oracle too.  The one exception is ``layernorm_from_output``,
+``ops/functional.py`` cannot hide in the oracle too.  The exceptions are ``layernorm_from_output``,
 which *is* a formula by definition: the yardstick for the memory-efficient LayerNorm backward is the
-fp64 evaluation of that form on the rounded output it is given.
+fp64 evaluation of that form on the rounded output it is given; and ``attention_staged``, the flash
+algorithm with its bf16 rounding points, which only measures what those roundings lose (it sets how
+tight a bound on a kernel can be, never what the right answer is).
 
 Column sums (dgamma, dbeta, dbias) come with a per-column scale: the sum over rows of the size of
 the column's summands.  Where a summand holds a computed row quantity (x-hat in dgamma, dy in dbias),
@@ -22,7 +25,7 @@ import math
 import torch
 import torch.nn.functional as F
 
-from distributed_training_and_deepspeed_amd.ops.rng import keep_mask  # noqa: F401  (re-exported for the tests)
+from distributed_training_and_deepspeed_amd.ops.rng import attn_keep_mask, keep_mask  # noqa: F401  (re-exported for the tests)
 
 TINY = 1e-30
 BF16, F32 = torch.bfloat16, torch.float32
@@ -369,3 +372,210 @@ def scale_cast(src, scale, dscale=None):
     if dscale is not None:
         s = s * float(f64(dscale).reshape(-1)[0])
     return f64(src) * s
+
+
+# ------------------------------------------------------------------------------------------
+# attention (ops/attention.py: qkv [B*S, (H + 2 Hkv) D], ctx [B*S, H D], lse [B, H, S])
+# ------------------------------------------------------------------------------------------
+def _rb(t):
+    """Round an fp64 tensor to bf16 and back (the kernels' rounding points of attention_staged)."""
+    return t.to(torch.bfloat16).to(torch.float64)
+
+
+def _attn_allowed(B, S, causal, key_range, doc_range):
+    """[B, 1, S, S] bool (query, key): True where the key takes part.  None: every key does."""
+    ok = None
+    j = torch.arange(S)
+    if causal:
+        ok = (j.view(1, S) <= j.view(S, 1)).view(1, 1, S, S).expand(B, 1, S, S)
+    if key_range is not None:
+        kr = key_range.detach().cpu().long().view(B, 2)
+        m = ((j.view(1, S) >= kr[:, :1]) & (j.view(1, S) < kr[:, 1:])).view(B, 1, 1, S).expand(B, 1, S, S)
+        ok = m if ok is None else ok & m
+    if doc_range is not None:
+        r = getattr(doc_range, "ranges", doc_range).detach().cpu().long().view(B, S, 2)
+        m = ((j.view(1, 1, S) >= r[:, :, :1]) & (j.view(1, 1, S) < r[:, :, 1:])).view(B, 1, S, S)
+        ok = m if ok is None else ok & m
+    return ok
+
+
+def _attn_scores(q, ke, D, S, slopes, ok):
+    """(scores with -inf for the keys left out, the same with 0 in rows that have no key, dead rows)."""
+    s = q @ ke.transpose(-1, -2) / math.sqrt(D)
+    if slopes is not None:
+        s = s + f64(slopes).view(1, -1, 1, 1) * torch.arange(S, dtype=torch.float64).view(1, 1, 1, S)
+    if ok is None:
+        return s, s, torch.zeros(s.shape[:-1], dtype=torch.bool)
+    s = s.masked_fill(~ok, -math.inf)
+    dead = ~ok.any(-1).expand(s.shape[:-1])
+    return s, s.masked_fill(dead[..., None], 0.0), dead
+
+
+def _attn_keep(keep, p, like):
+    """Dropout as a factor on the probabilities: keep / (1 - p), or None."""
+    if p <= 0 or keep is None:
+        return None
+    return f64(keep).view_as(like) / (1.0 - p)
+
+
+def attn_split(t, B, S, H, Hkv, D):
+    """A [B*S, (H + 2 Hkv) D] tensor (qkv or dqkv) as its q [B, S, H, D] and k, v [B, S, Hkv, D] views."""
+    x = t.reshape(B, S, H + 2 * Hkv, D)
+    return x[:, :, :H], x[:, :, H:H + Hkv], x[:, :, H + Hkv:]
+
+
+def _attn_scales(P, dP, dO, O, q, ke, scale, G):
+    """Row scales of dq [B, S, H] and dk [B, S, Hkv]: the size of the summands of dS = P (dP - delta)
+    times the largest element of the key / query row they multiply, with delta taken as sum_d |dO||O|
+    (|delta| would miss the cancellation inside delta itself)."""
+    w = P * (dP.abs() + (dO.abs() * O.abs()).sum(-1, keepdim=True))          # [B, H, S, S]
+    sc_dq = scale * (w * ke.abs().amax(-1)[:, :, None, :]).sum(-1)             # [B, H, S]
+    sc_dk = scale * (w * q.abs().amax(-1)[:, :, :, None]).sum(-2)              # [B, H, S] over the keys
+    B, H, S = sc_dk.shape
+    sc_dk = sc_dk.view(B, H // G, G, S).sum(2)
+    return sc_dq.transpose(1, 2), sc_dk.transpose(1, 2)
+
+
+def attention(qkv, dctx, B, S, H, D, causal=False, slopes=None, p=0.0, keep=None, key_range=None, doc_range=None,
+              kv_heads=None):
+    """Scaled-dot-product attention and its gradients for the loss sum(ctx * dctx), in fp64 from torch
+    operators and ``torch.autograd.grad``.  ``keep``: the [B, H, S, S] keep bits of ``ops.rng.
+    attn_keep_mask`` (an input).  Grouped-query attention is ``repeat_interleave`` inside the graph, so
+    autograd forms the group sum.  A row without a key has lse = -inf, ctx = 0 and takes part in no
+    gradient -- written as a rule (probabilities 0), not left to NaN arithmetic.
+
+    Returns ctx and dq [B, S, H, D] (one slice of the metric per (token, head) row: a kernel's [B*S, H D]
+    ctx is reshaped to it, never the other way), lse [B, H, S], dk / dv [B, S, Hkv, D], the row scales sc_dq
+    [B, S, H] and sc_dk [B, S, Hkv] (``_attn_scales``) and A [B, H, S] = max_j (scale sum_d |q||k| +
+    |slope j|) over the row's keys, the size of the scores behind the lse."""
+    Hkv = H if kv_heads is None else int(kv_heads)
+    G = H // Hkv
+    xl = _leaf(qkv).view(B, S, H + 2 * Hkv, D)
+    q, k, v = (t.transpose(1, 2) for t in attn_split(xl, B, S, H, Hkv, D))
+    ke, ve = k.repeat_interleave(G, 1), v.repeat_interleave(G, 1)
+    ok = _attn_allowed(B, S, causal, key_range, doc_range)
+    s, s0, dead = _attn_scores(q, ke, D, S, slopes, ok)
+    lse = torch.logsumexp(s0, -1).masked_fill(dead, -math.inf)
+    P = torch.softmax(s0, -1).masked_fill(dead[..., None], 0.0)
+    kf = _attn_keep(keep, p, P)
+    Pd = P if kf is None else P * kf
+    ctx = Pd @ ve                                                  # [B, H, S, D]
+    dO = f64(dctx).view(B, S, H, D).transpose(1, 2)
+    (g,) = torch.autograd.grad((ctx * dO).sum(), xl)
+    dq, dk, dv = attn_split(g, B, S, H, Hkv, D)
+    with torch.no_grad():
+        dP = dO @ ve.transpose(-1, -2)
+        if kf is not None:
+            dP = dP * kf
+        scale = 1.0 / math.sqrt(D)
+        sc_dq, sc_dk = _attn_scales(P, dP, dO, ctx, q, ke, scale, G)
+        a = scale * (q.abs() @ ke.abs().transpose(-1, -2))
+        if slopes is not None:
+            a = a + (f64(slopes).view(1, -1, 1, 1) * torch.arange(S, dtype=torch.float64).view(1, 1, 1, S)).abs()
+        if ok is not None:
+            a = a.masked_fill(~ok, 0.0)
+    return dict(ctx=ctx.detach().transpose(1, 2), lse=lse.detach(), dq=dq, dk=dk, dv=dv,
+                sc_dq=sc_dq, sc_dk=sc_dk, A=a.amax(-1))
+
+
+def attention_staged(qkv, dctx, B, S, H, D, causal=False, slopes=None, p=0.0, keep=None, key_range=None,
+                     doc_range=None, kv_heads=None):
+    """The flash kernels' algorithm in fp64 with bf16 rounding exactly where they round: P (after
+    dropout) before P V and P^T dO, dS before the dq / dk products, ctx before delta, and the outputs.
+    Like ``layernorm_from_output`` not an independent oracle: its distance from ``attention`` is what the
+    algorithm's rounding points have already lost on a given case.  Returns ctx, dq, dk, dv in the
+    oracle's [B, S, heads, D] shapes."""
+    Hkv = H if kv_heads is None else int(kv_heads)
+    G = H // Hkv
+    q, k, v = (t.transpose(1, 2) for t in attn_split(f64(qkv), B, S, H, Hkv, D))
+    ke, ve = k.repeat_interleave(G, 1), v.repeat_interleave(G, 1)
+    ok = _attn_allowed(B, S, causal, key_range, doc_range)
+    s, s0, dead = _attn_scores(q, ke, D, S, slopes, ok)
+    P = torch.softmax(s0, -1).masked_fill(dead[..., None], 0.0)
+    kf = _attn_keep(keep, p, P)
+    Pb = _rb(P if kf is None else P * kf)
+    dO = f64(dctx).view(B, S, H, D).transpose(1, 2)
+    ctx = _rb(Pb @ ve)
+    dv = Pb.transpose(-1, -2) @ dO
+    dP = dO @ ve.transpose(-1, -2)
+    if kf is not None:
+        dP = dP * kf
+    dS = _rb(P * (dP - (dO * ctx).sum(-1, keepdim=True)))
+    scale = 1.0 / math.sqrt(D)
+    dq = _rb(scale * (dS @ ke))
+    dk = scale * (dS.transpose(-1, -2) @ q)
+    dk, dv = (_rb(t.reshape(B, Hkv, G, S, D).sum(2)) for t in (dk, dv))
+    return dict(ctx=ctx.transpose(1, 2), dq=dq.transpose(1, 2), dk=dk.transpose(1, 2),
+                dv=dv.transpose(1, 2))
+
+
+# attention input regimes: f(B, S, H, D, Hkv, seed) -> (qkv, dctx) bf16 (so exact in fp32 too).  Positions
+# that depend on S are chosen per 64-key tile.
+SPIKE_MAGS = (1.0, 1.5, 2.5, 2.6)
+
+
+def spike_keys(S, descending=False):
+    """One spike key per 64-key tile, at a position that is not tile-aligned, with the magnitudes
+    1.0 / 1.5 / 2.5 / 2.6 (+2 per four tiles) ascending -- 8 c natural score units at D 64, so the
+    running maximum crosses the kernels' defer-max threshold (8 log2 units) at some tiles and stays
+    under it at others -- or the same magnitudes descending, from key 1 on."""
+    nt = (S + 63) // 64
+    pos = [64 * t + (5 + 13 * t) % min(64, S - 64 * t) for t in range(nt)]
+    mags = [SPIKE_MAGS[t % 4] + 2.0 * (t // 4) for t in range(nt)]
+    if descending:
+        pos[0], mags = 1, mags[::-1]
+    return list(zip(pos, mags))
+
+
+def _attn_randn(B, S, H, D, Hkv, seed):
+    g = torch.Generator().manual_seed(seed)
+    return (torch.randn(B, S, H + 2 * Hkv, D, generator=g, dtype=torch.float32),
+            torch.randn(B, S, H, D, generator=g, dtype=torch.float32))
+
+
+def _spiked(x, H, spikes):
+    """tests/test_attention_gpu.py ``_spiked_qkv``: half-scale inputs, every query of head 0 the
+    direction u = 1, and the K row c u at each spike position of key head 0 (V stays random, so a
+    wrongly weighted spike key shows in ctx)."""
+    x = x * 0.5
+    x[:, :, 0] = 1.0
+    for key, c in spikes:
+        x[:, key, H] = c
+    return x
+
+
+def attn_inputs(regime, B, S, H, D, kv_heads=None, seed=0):
+    Hkv = H if kv_heads is None else int(kv_heads)
+    x, d = _attn_randn(B, S, H, D, Hkv, seed)
+    i, h = torch.arange(S).view(1, S, 1, 1), torch.arange(H).view(1, 1, H, 1)
+    if regime == "gauss":
+        pass
+    elif regime == "peaked":                  # q, k x 2: score std 4
+        x[:, :, :H + Hkv] *= 2.0
+    elif regime == "onehot":                  # q, k x 4: score std 16, |lse| up to about 75
+        x[:, :, :H + Hkv] *= 4.0
+    elif regime == "row_scales":
+        # small query / dctx rows next to large ones.  The exponent is shifted per head ((i + 3h) mod 13,
+        # (i + 2h) mod 7, not i alone), so that the query heads of one GQA group differ in size at the
+        # same token and the dK / dV group sum adds terms up to 2^6 apart
+        x[:, :, :H] *= torch.exp2((((i + 3 * h) % 13) - 6) / 2.0)
+        d *= torch.exp2((((i + 2 * h) % 7) - 3).float())
+    elif regime == "k_offset":                # a large common-mode score: softmax is invariant
+        x[:, :, H:H + Hkv] += 4.0
+    elif regime == "spikes_up":
+        x = _spiked(x, H, spike_keys(S))
+    elif regime == "spikes_down":
+        x = _spiked(x, H, spike_keys(S, descending=True))
+    elif regime == "spike_at_edges":
+        x = _spiked(x, H, [(0, 2.5), (S - 1, 2.6)])
+    elif regime == "zero_rows":
+        x[:, 0::5, :H] = 0.0
+        d[:, 0::7] = 0.0
+        x[:, S // 2, H + Hkv:] = 0.0
+    else:
+        raise ValueError(regime)
+    return (x.reshape(B * S, (H + 2 * Hkv) * D).to(torch.bfloat16), d.reshape(B * S, H * D).to(torch.bfloat16))
+
+
+ATTN_REGIMES = ("gauss", "peaked", "onehot", "row_scales", "k_offset", "spikes_up", "spikes_down", "spike_at_edges",
+                "zero_rows")
