@@ -43,6 +43,7 @@ class TransformerConfig:
     norm: str = "layer"               # "layer" (LayerNorm) | "rms" (RMSNorm: no mean, no beta)
     rope_theta: float = 0.0           # rotary position embedding base; 0 = off
     num_kv_heads: int = 0             # grouped-query attention (Llama family): key/value heads; 0 = num_heads
+    sliding_window: int = 0           # causal sliding-window attention (Mistral): keys per query, own included; 0 = off
     # activation "swiglu": the gated MLP down(silu(gate(x)) * up(x)), three weights, no bias
 
     def __post_init__(self):
@@ -69,6 +70,11 @@ class TransformerConfig:
                              "models/llama.py::LlamaLayer only")
         if self.kv_heads != self.num_heads and self.attn_dropout > 0:
             raise ValueError("grouped-query attention has no attention dropout: attn_dropout must be 0")
+        if self.sliding_window < 0:
+            raise ValueError(f"sliding_window = {self.sliding_window} must be >= 0 (0 = off)")
+        if self.sliding_window and not (self.llama_style and self.causal and self.attn_dropout == 0):
+            raise ValueError("a sliding window (sliding_window > 0) is implemented by models/llama.py::LlamaLayer "
+                             "only, for causal models without attention dropout")
 
     @property
     def kv_heads(self) -> int:
@@ -137,8 +143,9 @@ CAUSAL_TINY = GPT2_MEDIUM.with_(name="causal-tiny", vocab_size=1024, hidden_size
 # Llama family (HF LlamaForCausalLM): RMSNorm, rotary embeddings, SwiGLU MLP, no biases, no position
 # table, untied head.  num_kv_heads < num_heads: grouped-query attention (TinyLlama, Llama-3).  Parameter
 # counts (tests/test_llama_cpu.py, tests/test_gqa_cpu.py): 2 V h + L (2 h^2 + 2 h Hkv D + 3 h f + 2 h) + h,
-# with Hkv D = h for multi-head attention.  Llama-3.1 / 3.2 (rotary scaling) and Mistral (sliding window)
-# are not described here.
+# with Hkv D = h for multi-head attention.  Mistral is a grouped-query Llama with sliding_window keys per
+# query (HF MistralForCausalLM; the tensor names are Llama's).  Llama-3.1 / 3.2 (rotary scaling) are not
+# described here.
 LLAMA_160M = TransformerConfig(
     name="JackFram/llama-160m", family="llama", vocab_size=32000, hidden_size=768, num_layers=12,
     num_heads=12, ffn_size=3072, max_positions=2048, activation="swiglu", pre_ln=True, causal=True,
@@ -159,12 +166,16 @@ LLAMA_3_8B = LLAMA_160M.with_(name="meta-llama/Meta-Llama-3-8B", vocab_size=1282
                               rope_theta=500000.0)
 LLAMA_TINY_GQA = LLAMA_160M.with_(name="llama-tiny-gqa", vocab_size=1024, hidden_size=256, num_layers=2, num_heads=4,
                                   num_kv_heads=2, ffn_size=768, max_positions=512)
+# sliding window
+MISTRAL_7B = LLAMA_160M.with_(name="mistralai/Mistral-7B-v0.1", hidden_size=4096, num_layers=32, num_heads=32,
+                              num_kv_heads=8, ffn_size=14336, max_positions=32768, ln_eps=1e-5, sliding_window=4096)
+MISTRAL_TINY = LLAMA_TINY_GQA.with_(name="mistral-tiny", sliding_window=48)
 
 PRESETS = {
     c.name: c
     for c in (BERT_BASE, BERT_LARGE, BERT_TINY, BLOOM_560M, OPT_125M, GPT2_MEDIUM, W4_BLOCK,
               CAUSAL_TINY, LLAMA_160M, SHEARED_LLAMA_1_3B, LLAMA_2_7B, LLAMA_TINY, TINYLLAMA_1_1B, LLAMA_3_8B,
-              LLAMA_TINY_GQA)
+              LLAMA_TINY_GQA, MISTRAL_7B, MISTRAL_TINY)
 }
 ALIASES = {
     "base": "bert-base-cased", "large": "bert-large-cased", "tiny": "bert-tiny",
@@ -174,10 +185,15 @@ ALIASES = {
     "llama-160m": "JackFram/llama-160m", "sheared-llama-1.3b": "princeton-nlp/Sheared-LLaMA-1.3B",
     "llama-2-7b": "meta-llama/Llama-2-7b-hf",
     "tinyllama-1.1b": "TinyLlama/TinyLlama_v1.1", "llama-3-8b": "meta-llama/Meta-Llama-3-8B",
+    "mistral-7b": "mistralai/Mistral-7B-v0.1",
 }
 
 
-def get_config(name: str) -> TransformerConfig:
+def get_config(name: str | TransformerConfig) -> TransformerConfig:
+    """The preset of that name or alias; a ``TransformerConfig`` (a preset altered with ``with_``) is
+    returned as it is, so whatever takes a preset's name takes such a config too."""
+    if isinstance(name, TransformerConfig):
+        return name
     key = ALIASES.get(name, name)
     if key not in PRESETS:
         raise KeyError(f"unknown model preset {name!r}; known: {sorted(PRESETS) + sorted(ALIASES)}")

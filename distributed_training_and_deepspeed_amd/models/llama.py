@@ -25,7 +25,11 @@ Hkv heads and query head i reads key/value head i // (H / Hkv) (HF's ``repeat_kv
 expands K / V: the rotary kernel rotates the H + Hkv heads of the q and k blocks and the attention kernels
 address K / V by group (ops/attention.py, ``kv_heads``).
 
-Rotary scaling, a sliding window and a KV cache are not implemented.
+Sliding window (``cfg.sliding_window`` = W > 0, Mistral): query i attends the W keys i - W < j <= i,
+intersected with the key range / document span.  The fused path hands W to the attention kernels
+(ops/attention.py, ``window``), which visit only the band's tiles; the reference masks the band.
+
+Rotary scaling and a KV cache are not implemented.
 """
 from __future__ import annotations
 
@@ -141,6 +145,8 @@ class LlamaLayer(nn.Module):
         s = torch.matmul(q, k.transpose(-1, -2)) * (1.0 / math.sqrt(D))
         if c.causal:
             s = s.masked_fill(torch.ones(S, S, dtype=torch.bool, device=s.device).triu(1), float("-inf"))
+        if c.sliding_window:     # key j <= i - W lies behind query i's window
+            s = s.masked_fill(torch.ones(S, S, dtype=torch.bool, device=s.device).tril(-c.sliding_window), float("-inf"))
         if key_range is not None or doc_range is not None:
             outside = A._range_mask(key_range, B, S, s.device) if key_range is not None \
                 else A._doc_mask(doc_range, B, S, s.device)
@@ -184,7 +190,8 @@ class _FusedLlamaLayerFn(torch.autograd.Function):
         qkv = _linear(a_in, qkv_w)
         Fx.rope_(qkv, table, B, S, H, D, pos=position_ids, kv_heads=Hkv)   # in place: the rotated qkv is what is kept
         actx, lse, amask = A.attn_fwd(qkv, B, S, H, D, c.causal, None, p_a, rng, sa,
-                                      key_range=key_range, doc_range=doc_range, kv_heads=Hkv)
+                                      key_range=key_range, doc_range=doc_range, kv_heads=Hkv,
+                                      window=c.sliding_window or None)
         o = _linear(actx, o_w)
         z1, f_in, r2 = Fx.rms_fwd(o, x2d, g2, eps)             # z1 = x + o and RMS2(z1) in one pass
         gu = _linear(f_in, gu_w)
@@ -230,7 +237,8 @@ class _FusedLlamaLayerFn(torch.autograd.Function):
         emit_wgrad(o_w, dz1, actx, async_ok=True)
         dctx = _dgrad(dz1, o_w)
         dqkv = A.attn_bwd(dctx, qkv, actx, lse, B, S, H, D, c.causal, None, p_a, rng, sa, ctx.amask,
-                          key_range=ctx.key_range, doc_range=ctx.doc_range, kv_heads=ctx.kv_heads)
+                          key_range=ctx.key_range, doc_range=ctx.doc_range, kv_heads=ctx.kv_heads,
+                          window=c.sliding_window or None)
         # the rotation's adjoint is its inverse: dqkv back in front of the rotary embedding
         Fx.rope_(dqkv, ctx.table, B, S, H, D, pos=ctx.position_ids, inverse=True, kv_heads=ctx.kv_heads)
         emit_wgrad(qkv_w, dqkv, a_in, async_ok=True)
@@ -248,7 +256,9 @@ def from_hf_state_dict(sd: dict) -> dict:
     """HF ``LlamaForCausalLM`` state dict -> ``CausalLM`` (Llama family) state dict: keys renamed,
     q/k/v and gate/up concatenated along the output rows -- a grouped-query checkpoint's k_proj / v_proj
     simply have fewer rows.  ``rotary_emb.inv_freq`` buffers of older checkpoints are dropped; a tied
-    checkpoint (no ``lm_head.weight``) gets the embedding table."""
+    checkpoint (no ``lm_head.weight``) gets the embedding table.  An HF ``MistralForCausalLM`` state dict
+    converts unchanged, here and in ``to_hf_state_dict``: its tensor names are Llama's, and the sliding
+    window is a matter of the config (``sliding_window``), not of the weights."""
     out = {"embeddings.word": sd["model.embed_tokens.weight"],
            "final_ln.weight": sd["model.norm.weight"],
            "head.own_weight": sd["lm_head.weight"] if "lm_head.weight" in sd else sd["model.embed_tokens.weight"]}

@@ -95,6 +95,9 @@ _SIGS = {
     # then B, S, H, Hkv, D, ld, ldo, causal, scale, the key ranges or null, the doc array or null)
     "dtd_attn_fwd_gqa": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, F, P, P, P]),
     "dtd_attn_bwd_gqa": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, F, P, P, P]),
+    # (the _win forms, sliding window: the _gqa arguments with the window behind the scale; 1 <= Hkv <= H)
+    "dtd_attn_fwd_win": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, F, I, P, P, P]),
+    "dtd_attn_bwd_win": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, F, I, P, P, P]),
     "dtd_attn_masks": (I, [P, I, I, I, F, P, U32, P]),
     "dtd_attn_set_bwd_form": (I, [I]),
     "dtd_attn_set_bwd_kernels": (I, [I]),

@@ -31,6 +31,16 @@ per query head.  The causal mask, ``key_range`` and ``doc_range`` apply as above
 are not supported together with ``Hkv != H`` (``ValueError``).  ``kv_heads`` None or H is the
 multi-head layout above, on its own code paths.
 
+Sliding window: ``window = W`` (an integer > 0, ``causal=True`` only) lets query i attend key j iff
+i - W < j <= i -- W keys including the query's own, HF Mistral's ``sliding_window``.  It composes by
+intersection with ``key_range`` (additionally lo <= j < hi) and ``doc_range`` (additionally j inside
+i's document); a row left without a key -- e.g. i >= hi + W - 1 under a right-padded range (0, hi) --
+follows the empty-row rule above, and keys no query sees get dk = dv = 0.  Neither dropout nor ALiBi
+(``ValueError``).  The bf16 kernels are windowed instantiations of the grouped-query family, which
+visit only the O(S W) band of key tiles; the multi-head layout runs through them with one query head
+per group (its q | k | v blocks are that layout).  ``window`` None, 0 or >= S is the call without
+the argument, on its code paths and bit for bit.
+
 Reference semantics: HF BertSelfAttention eager path (matmul, softmax, dropout, matmul --
 SURVEY.md K2, reference model/transformer.py:80-86); the reference never passes an
 attention mask for BERT (data_parallel_training.py:53), so by default (no ``key_range``) padding
@@ -93,6 +103,29 @@ def _gqa_entry(name: str) -> str:
     if not _lib.has(name):
         raise _lib.KernelError("the kernel library has no grouped-query attention entry points (stale build)")
     return name
+
+
+def _win_entry(name: str) -> str:
+    if not _lib.has(name):
+        raise _lib.KernelError("the kernel library has no sliding-window attention entry points (stale build)")
+    return name
+
+
+def _window(window, S: int, causal, p, slopes) -> int:
+    """The effective window of a call: 0 = none (None, 0, or >= S, where the band is the whole causal
+    triangle); otherwise validated (module docstring)."""
+    if window is None:
+        return 0
+    if isinstance(window, bool) or int(window) != window or window < 0:
+        raise ValueError(f"window must be a positive integer (or None / 0 for no window), got {window!r}")
+    window = int(window)
+    if window == 0:
+        return 0
+    if not causal:
+        raise ValueError("a sliding window needs causal=True (a symmetric local window is not supported)")
+    if p > 0 or slopes is not None:
+        raise ValueError("a sliding window supports neither dropout nor ALiBi")
+    return 0 if window >= S else window
 
 
 def _cdt(t: torch.Tensor) -> torch.dtype:
@@ -231,7 +264,7 @@ def _probs(s, lse):
     return torch.exp(s - lse.masked_fill(lse == float("-inf"), 0.0))
 
 
-def _scores(q, k, scale, causal, slopes, key_range=None, doc_range=None):
+def _scores(q, k, scale, causal, slopes, key_range=None, doc_range=None, window: int = 0):
     _exclusive(key_range, doc_range)
     c = _cdt(q)
     s = torch.matmul(q.to(c), k.to(c).transpose(-1, -2)) * scale
@@ -241,6 +274,8 @@ def _scores(q, k, scale, causal, slopes, key_range=None, doc_range=None):
     if causal:
         m = torch.ones(S, S, dtype=torch.bool, device=s.device).triu(1)
         s = s.masked_fill(m, float("-inf"))
+    if window:       # the band: key j <= i - window lies behind query i's window
+        s = s.masked_fill(torch.ones(S, S, dtype=torch.bool, device=s.device).tril(-window), float("-inf"))
     if key_range is not None:
         s = s.masked_fill(_range_mask(key_range, q.shape[0], S, s.device), float("-inf"))
     if doc_range is not None:
@@ -254,16 +289,17 @@ def _drop_mask(B, H, S, p, rng, sid, device):
 
 
 def attn_fwd_ref(qkv, B, S, H, D, causal=False, slopes=None, p=0.0, rng: RngState | None = None, sid=0,
-                 scale=None, key_range=None, doc_range=None, kv_heads: int | None = None):
+                 scale=None, key_range=None, doc_range=None, kv_heads: int | None = None, window: int | None = None):
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     Hkv = _kv_heads(kv_heads, H)
+    window = _window(window, S, causal, p, slopes)
     if Hkv != H:     # K / V expanded to the H query heads (repeat_kv order)
         _check_gqa(qkv, B, S, H, Hkv, D, p, slopes)
         q, k, v = _split_gqa(qkv, B, S, H, Hkv, D)
         k, v = k.repeat_interleave(H // Hkv, 1), v.repeat_interleave(H // Hkv, 1)
     else:
         q, k, v = _split(qkv, B, S, H, D)
-    s = _scores(q, k, scale, causal, slopes, key_range, doc_range)
+    s = _scores(q, k, scale, causal, slopes, key_range, doc_range, window)
     lse = torch.logsumexp(s, -1)       # -inf for a row without a key
     prob = _probs(s, lse)
     if p > 0:
@@ -273,16 +309,17 @@ def attn_fwd_ref(qkv, B, S, H, D, causal=False, slopes=None, p=0.0, rng: RngStat
 
 
 def attn_bwd_ref(dctx, qkv, ctx, lse, B, S, H, D, causal=False, slopes=None, p=0.0, rng=None, sid=0, scale=None,
-                 key_range=None, doc_range=None, kv_heads: int | None = None):
+                 key_range=None, doc_range=None, kv_heads: int | None = None, window: int | None = None):
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     Hkv = _kv_heads(kv_heads, H)
+    window = _window(window, S, causal, p, slopes)
     if Hkv != H:
         _check_gqa(qkv, B, S, H, Hkv, D, p, slopes)
         q, k, v = _split_gqa(qkv, B, S, H, Hkv, D)
         k, v = k.repeat_interleave(H // Hkv, 1), v.repeat_interleave(H // Hkv, 1)
     else:
         q, k, v = _split(qkv, B, S, H, D)
-    s = _scores(q, k, scale, causal, slopes, key_range, doc_range)
+    s = _scores(q, k, scale, causal, slopes, key_range, doc_range, window)
     prob = _probs(s, lse)
     c = s.dtype
     do = dctx.view(B, S, H, D).transpose(1, 2).to(c)
@@ -344,10 +381,10 @@ def fused_bwd_built() -> bool:
     return _lib.has("dtd_attn_fused_bwd_built") and bool(_lib.lib().dtd_attn_fused_bwd_built())
 
 
-def fused_bwd_applies(S: int, D: int, causal: bool, slopes, key_range=None, doc_range=None) -> bool:
-    """Whether ``attn_bwd`` may take a one-kernel form; never with a key range or document spans
-    (split pair only)."""
-    return (key_range is None and doc_range is None and D == 64 and not causal and slopes is None and S % 128 == 0 and S <= 512
+def fused_bwd_applies(S: int, D: int, causal: bool, slopes, key_range=None, doc_range=None, window=None) -> bool:
+    """Whether ``attn_bwd`` may take a one-kernel form; never with a key range, document spans or a
+    sliding window (split pair only)."""
+    return (not window and key_range is None and doc_range is None and D == 64 and not causal and slopes is None and S % 128 == 0 and S <= 512
             and fused_bwd_built())
 
 
@@ -473,7 +510,8 @@ def attn_masks_async(B, S, H, D, p, rng: RngState, sid, device) -> PendingMasks 
 
 def attn_fwd(qkv, B, S, H, D, causal=False, slopes=None, p=0.0, rng: RngState | None = None, sid=0,
              masks: PendingMasks | None = None, key_range: torch.Tensor | None = None,
-             doc_range: DocRange | torch.Tensor | None = None, kv_heads: int | None = None):
+             doc_range: DocRange | torch.Tensor | None = None, kv_heads: int | None = None,
+             window: int | None = None):
     """Returns (ctx [B*S, H*D], lse [B, H, S] fp32, masks).  ``masks`` holds the dropout keep
     bits for the backward ([2, B*H*S*ceil(S/32)] int32 on the kernel path, None otherwise);
     pass the ``attn_masks_async`` result to reuse masks generated ahead on a side stream.
@@ -488,9 +526,16 @@ def attn_fwd(qkv, B, S, H, D, causal=False, slopes=None, p=0.0, rng: RngState | 
 
     ``kv_heads``: grouped-query attention (module docstring): qkv is ``[B*S, (H + 2*Hkv)*D]``.  The
     bf16 kernels read each query head's K/V tiles from its group's head; fp32 inputs take the math
-    reference.  None or H: the multi-head path, exactly as without the argument."""
+    reference.  None or H: the multi-head path, exactly as without the argument.
+
+    ``window``: causal sliding window of that many keys per query (module docstring).  The bf16
+    kernels visit only the band's key tiles; fp32 and CPU inputs take the math reference.  None, 0 or
+    >= S: exactly the call without the argument."""
     _exclusive(key_range, doc_range)
     Hkv = _kv_heads(kv_heads, H)
+    window = _window(window, S, causal, p, slopes)
+    if window:       # (p = 0 here, so there are no keep bits to join)
+        return _attn_fwd_win(qkv, B, S, H, Hkv, D, window, key_range, doc_range)
     if Hkv != H:
         return _attn_fwd_gqa(qkv, B, S, H, Hkv, D, causal, slopes, p, key_range, doc_range)
     if (key_range is not None or doc_range is not None) and qkv.dtype == torch.float32:
@@ -537,7 +582,8 @@ def attn_fwd(qkv, B, S, H, D, causal=False, slopes=None, p=0.0, rng: RngState | 
 
 def attn_bwd(dctx, qkv, ctx, lse, B, S, H, D, causal=False, slopes=None, p=0.0, rng=None, sid=0, masks=None,
              dbias=None, key_range: torch.Tensor | None = None,
-             doc_range: DocRange | torch.Tensor | None = None, kv_heads: int | None = None):
+             doc_range: DocRange | torch.Tensor | None = None, kv_heads: int | None = None,
+             window: int | None = None):
     """Returns dqkv [B*S, 3*H*D] in the qkv layout.  ``dbias`` = (dst, acc): also writes the
     column sums of dqkv (the qkv projection's bias gradient) -- on the kernel path as per-wave
     partials from the dQ / dK,dV epilogues (no extra pass over dqkv).
@@ -551,10 +597,19 @@ def attn_bwd(dctx, qkv, ctx, lse, B, S, H, D, causal=False, slopes=None, p=0.0, 
 
     ``kv_heads``: the forward's (grouped-query attention): dqkv is ``[B*S, (H + 2*Hkv)*D]``; one
     dK/dV workgroup per (key block, key/value head) sums its group's query heads in registers.
-    ``dbias`` then takes the column sums in a pass of its own (``bias_grad``)."""
+    ``dbias`` then takes the column sums in a pass of its own (``bias_grad``).
+
+    ``window``: the forward's sliding window: the split kernels of the windowed family, whose dK/dV
+    workgroups stop at the last query that sees one of their keys; ``dbias`` as with ``kv_heads``."""
     from . import functional as Fx
     _exclusive(key_range, doc_range)
     Hkv = _kv_heads(kv_heads, H)
+    window = _window(window, S, causal, p, slopes)
+    if window:
+        dqkv = _attn_bwd_win(dctx, qkv, ctx, lse, B, S, H, Hkv, D, window, key_range, doc_range)
+        if dbias is not None:
+            Fx.bias_grad(dqkv, *dbias)
+        return dqkv
     if Hkv != H:
         dqkv = _attn_bwd_gqa(dctx, qkv, ctx, lse, B, S, H, Hkv, D, causal, slopes, p, key_range, doc_range)
         if dbias is not None:
@@ -650,6 +705,52 @@ def _attn_bwd_gqa(dctx, qkv, ctx, lse, B, S, H, Hkv, D, causal, slopes, p, key_r
     krp, docp, _keep = _gqa_ranges(key_range, doc_range, B, S, qkv.device)
     _lib.call(name, qb, qb + ko, qb + vo, ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr(), delta.data_ptr(),
               gb, gb + ko, gb + vo, B, S, H, Hkv, D, ld, H * D, int(causal), 1.0 / math.sqrt(D), krp, docp,
+              _lib.stream())
+    return dqkv
+
+
+def _win_kernel(qkv, B, S, H, Hkv, D, name: str) -> bool:
+    """Whether a windowed call runs the kernels: bf16 on the GPU with D 64 / 128; fp32, CPU and other
+    head dims take the math reference.  A GPU build without the entry points is an error."""
+    if qkv.numel() != B * S * (H + 2 * Hkv) * D:
+        raise ValueError(f"qkv must be [B*S, (H + 2*Hkv)*D] = [{B * S}, {(H + 2 * Hkv) * D}], got {tuple(qkv.shape)}")
+    if not (qkv.is_cuda and qkv.dtype == torch.bfloat16 and D in (64, 128)):
+        return False
+    _win_entry(name)
+    return True
+
+
+def _attn_fwd_win(qkv, B, S, H, Hkv, D, window, key_range, doc_range):
+    name = "dtd_attn_fwd_win"
+    if not _win_kernel(qkv, B, S, H, Hkv, D, name):
+        ctx, lse = attn_fwd_ref(qkv, B, S, H, D, True, key_range=key_range, doc_range=doc_range, kv_heads=Hkv,
+                                window=window)
+        return ctx, lse, None
+    qkv = qkv.contiguous()
+    ctx = torch.empty((B * S, H * D), dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty((B, H, S), dtype=torch.float32, device=qkv.device)
+    # Hkv = H: [B, S, 3, H, D] is the q | k | v block layout with one query head per group
+    ld, es, base = (H + 2 * Hkv) * D, qkv.element_size(), qkv.data_ptr()
+    krp, docp, _keep = _gqa_ranges(key_range, doc_range, B, S, qkv.device)
+    _lib.call(name, base, base + H * D * es, base + (H + Hkv) * D * es, ctx.data_ptr(), lse.data_ptr(), B, S, H, Hkv,
+              D, ld, H * D, 1, 1.0 / math.sqrt(D), window, krp, docp, _lib.stream())
+    return ctx, lse, None
+
+
+def _attn_bwd_win(dctx, qkv, ctx, lse, B, S, H, Hkv, D, window, key_range, doc_range):
+    name = "dtd_attn_bwd_win"
+    if not _win_kernel(qkv, B, S, H, Hkv, D, name):
+        return attn_bwd_ref(dctx, qkv, ctx, lse, B, S, H, D, True, key_range=key_range, doc_range=doc_range,
+                            kv_heads=Hkv, window=window)
+    dctx = dctx.contiguous()
+    dqkv = torch.empty_like(qkv)
+    delta = torch.empty((B, H, S), dtype=torch.float32, device=qkv.device)
+    ld, es = (H + 2 * Hkv) * D, qkv.element_size()
+    qb, gb = qkv.data_ptr(), dqkv.data_ptr()
+    ko, vo = H * D * es, (H + Hkv) * D * es
+    krp, docp, _keep = _gqa_ranges(key_range, doc_range, B, S, qkv.device)
+    _lib.call(name, qb, qb + ko, qb + vo, ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr(), delta.data_ptr(),
+              gb, gb + ko, gb + vo, B, S, H, Hkv, D, ld, H * D, 1, 1.0 / math.sqrt(D), window, krp, docp,
               _lib.stream())
     return dqkv
 

@@ -42,6 +42,12 @@
 // forms (dtd_attn_fwd_gqa / dtd_attn_bwd_gqa only; no dropout, no ALiBi) keep the forward's and dQ's
 // grid and read their K/V tiles from head h / G; dK/dV runs on grid (ceil(S/128), B*Hkv) and sums
 // its group's G query heads in the accumulators.  ctx, lse and delta stay per query head.
+//
+// Sliding window (causal; query i sees the `window` keys i - window < j <= i, intersected with the key
+// range or document span): the *_win_kernel forms (dtd_attn_fwd_win / dtd_attn_bwd_win only) are the
+// grouped-query forms with tile bounds that move with the block -- the forward and dQ start at the
+// first key of the block's first query, dK/dV stops at the last query of the block's last key -- so a
+// call costs O(S window) tiles.  1 <= Hkv <= H: the multi-head layout is the grouped one with G = 1.
 #include <stdio.h>
 #include <type_traits>
 #include <stdlib.h>
@@ -193,7 +199,8 @@ struct FwdArgs {
   // half-open span (lo, hi) of each position's document ((0, 0) for a pad), followed at once by
   // [B][ceil(S/128)][2] = (min lo, max hi) over each 128-position block's non-empty rows ((0, 0) for
   // a block without one).  // GQA kernels (no dropout, so no keep words) likewise read Hkv, the number of key/value heads,
-  // from W -- here and in BwdArgs.
+  // from W -- here and in BwdArgs.  The sliding-window kernels (grouped-query forms, so no dropout
+  // either) read the window, an integer, from the bits of p -- here and in BwdArgs.
 };
 
 // Key range of sequence b, clamped to [0, S]; b is workgroup-uniform, so both are scalar loads and
@@ -216,12 +223,21 @@ struct DocSpan {
   __device__ __forceinline__ bool has(int j) const { return (unsigned)(j - lo) < (unsigned)len; }
   // the span covers [j0, j0 + n)
   __device__ __forceinline__ bool covers(int j0, int n) const { return j0 >= lo && j0 + n - lo <= len; }
+  // intersection with [l, inf) / with (-inf, h) (the sliding-window forms; an empty span stays empty)
+  __device__ __forceinline__ void clip_lo(int l) {
+    l = max(lo, l);
+    len = max(len - (l - lo), 0);
+    lo = l;
+  }
+  __device__ __forceinline__ void clip_hi(int h) { len = max(min(len, h - lo), 0); }
 };
 // what the kernels without document spans hold in its place: nothing
 struct NoSpan {
   __device__ __forceinline__ NoSpan& operator=(const DocSpan&) { return *this; }   // (only in discarded branches)
   __device__ __forceinline__ bool has(int) const { return true; }
   __device__ __forceinline__ bool covers(int, int) const { return true; }
+  __device__ __forceinline__ void clip_lo(int) {}
+  __device__ __forceinline__ void clip_hi(int) {}
 };
 template <bool DOC> using SpanOf = std::conditional_t<DOC, DocSpan, NoSpan>;
 
@@ -510,12 +526,12 @@ struct TileLoader {
 // so that the instantiations without it keep their symbols; both include attention_fwd_body.h.
 template <int D, int OCC, int BN, int RING, bool PK = false, bool RANGE = false>
 __global__ void __launch_bounds__(256, OCC) attn_fwd_kernel(FwdArgs a) {
-  constexpr bool DOC = false, GQA = false;
+  constexpr bool DOC = false, GQA = false, WIN = false;
 #include "attention_fwd_body.h"
 }
 template <int D, int OCC, int BN, int RING>
 __global__ void __launch_bounds__(256, OCC) attn_fwd_doc_kernel(FwdArgs a) {
-  constexpr bool PK = false, RANGE = false, DOC = true, GQA = false;
+  constexpr bool PK = false, RANGE = false, DOC = true, GQA = false, WIN = false;
 #include "attention_fwd_body.h"
 }
 // Grouped-query form (Hkv < H key/value heads, query head h reads key/value head h / (H / Hkv)): a
@@ -523,7 +539,20 @@ __global__ void __launch_bounds__(256, OCC) attn_fwd_doc_kernel(FwdArgs a) {
 // ALiBi; the argument block is FwdArgs as it stands, with Hkv in the (then unused) field W.
 template <int D, int OCC, int BN, int RING, int MODE>
 __global__ void __launch_bounds__(256, OCC) attn_fwd_gqa_kernel(FwdArgs a) {
-  constexpr bool PK = false, RANGE = MODE == 1, DOC = MODE == 2, GQA = true;
+  constexpr bool PK = false, RANGE = MODE == 1, DOC = MODE == 2, GQA = true, WIN = false;
+#include "attention_fwd_body.h"
+}
+// Sliding-window form of the grouped-query kernel (dtd_attn_fwd_win; causal only): query i sees key j
+// iff i - win < j <= i, intersected with MODE's key range / document span.  A kernel of its own name
+// once more.  The window is an integer carried in FwdArgs::p (no dropout here), Hkv in W as above;
+// Hkv = H (G = 1) is the multi-head layout.  The key tiles start at floor(max(lo, qblk - win + 1) / BN);
+// a tile whose first key the wave's last query no longer sees takes the masked path.  The waves of a
+// block start seeing keys at different tiles, so a wave can meet leading tiles it masks whole while
+// m = -inf: the defer-max vote's NaN difference takes the rescale, which leaves m = -inf, l = 0, O = 0
+// (as under a causal left-padded range).  MODE 2 folds the window into the lane's span when it is loaded.
+template <int D, int OCC, int BN, int RING, int MODE>
+__global__ void __launch_bounds__(256, OCC) attn_fwd_win_kernel(FwdArgs a) {
+  constexpr bool PK = false, RANGE = MODE == 1, DOC = MODE == 2, GQA = true, WIN = true;
 #include "attention_fwd_body.h"
 }
 
@@ -772,12 +801,12 @@ __device__ __forceinline__ int colsum_col(int k, int hh) { return (k >> 4) * 32 
 // below.)
 template <int D, int OCC, int BM, bool DROP, bool ALIBI, bool MASK = true, bool RANGE = false>
 __global__ void __launch_bounds__(256, OCC) attn_bwd_dkdv_kernel(BwdArgs a) {
-  constexpr bool DOC = false, GQA = false;
+  constexpr bool DOC = false, GQA = false, WIN = false;
 #include "attention_bwd_dkdv_body.h"
 }
 template <int D, int OCC, int BM, bool DROP, bool ALIBI>
 __global__ void __launch_bounds__(256, OCC) attn_bwd_dkdv_doc_kernel(BwdArgs a) {
-  constexpr bool MASK = true, RANGE = false, DOC = true, GQA = false;
+  constexpr bool MASK = true, RANGE = false, DOC = true, GQA = false, WIN = false;
 #include "attention_bwd_dkdv_body.h"
 }
 // Grouped-query form: grid (ceil(S/128), B * Hkv).  A workgroup keeps its 128 keys' K/V fragments
@@ -787,7 +816,16 @@ __global__ void __launch_bounds__(256, OCC) attn_bwd_dkdv_doc_kernel(BwdArgs a) 
 // attn_fwd_gqa_kernel; Hkv in BwdArgs::W.
 template <int D, int OCC, int BM, int MODE>
 __global__ void __launch_bounds__(256, OCC) attn_bwd_dkdv_gqa_kernel(BwdArgs a) {
-  constexpr bool DROP = false, ALIBI = false, MASK = true, RANGE = MODE == 1, DOC = MODE == 2, GQA = true;
+  constexpr bool DROP = false, ALIBI = false, MASK = true, RANGE = MODE == 1, DOC = MODE == 2, GQA = true, WIN = false;
+#include "attention_bwd_dkdv_body.h"
+}
+// Sliding-window form (see attn_fwd_win_kernel; the window in BwdArgs::p): key j is seen by the
+// queries j <= q < j + win, so the query tiles end at min(qend, kblk + 127 + win) -- the same count
+// for every head of the group, so the seam logic stands -- and a 32-query sub-block whose last query
+// lies past the window of the block's first key is masked.  MODE 2 folds the window into the key's span.
+template <int D, int OCC, int BM, int MODE>
+__global__ void __launch_bounds__(256, OCC) attn_bwd_dkdv_win_kernel(BwdArgs a) {
+  constexpr bool DROP = false, ALIBI = false, MASK = true, RANGE = MODE == 1, DOC = MODE == 2, GQA = true, WIN = true;
 #include "attention_bwd_dkdv_body.h"
 }
 
@@ -801,17 +839,23 @@ __global__ void __launch_bounds__(256, OCC) attn_bwd_dkdv_gqa_kernel(BwdArgs a) 
 // (attn_bwd_dq_doc_kernel, below).
 template <int D, int OCC, int BN, int RING, bool PK = false, bool RANGE = false>
 __global__ void __launch_bounds__(256, OCC) attn_bwd_dq_kernel(BwdArgs a) {
-  constexpr bool DOC = false, GQA = false;
+  constexpr bool DOC = false, GQA = false, WIN = false;
 #include "attention_bwd_dq_body.h"
 }
 template <int D, int OCC, int BN, int RING>
 __global__ void __launch_bounds__(256, OCC) attn_bwd_dq_doc_kernel(BwdArgs a) {
-  constexpr bool PK = false, RANGE = false, DOC = true, GQA = false;
+  constexpr bool PK = false, RANGE = false, DOC = true, GQA = false, WIN = false;
 #include "attention_bwd_dq_body.h"
 }
 template <int D, int OCC, int BN, int RING, int MODE>
 __global__ void __launch_bounds__(256, OCC) attn_bwd_dq_gqa_kernel(BwdArgs a) {
-  constexpr bool PK = false, RANGE = MODE == 1, DOC = MODE == 2, GQA = true;
+  constexpr bool PK = false, RANGE = MODE == 1, DOC = MODE == 2, GQA = true, WIN = false;
+#include "attention_bwd_dq_body.h"
+}
+// sliding window: tile range and masks as in attn_fwd_win_kernel
+template <int D, int OCC, int BN, int RING, int MODE>
+__global__ void __launch_bounds__(256, OCC) attn_bwd_dq_win_kernel(BwdArgs a) {
+  constexpr bool PK = false, RANGE = MODE == 1, DOC = MODE == 2, GQA = true, WIN = true;
 #include "attention_bwd_dq_body.h"
 }
 
@@ -1535,6 +1579,39 @@ DTD_EXPORT int dtd_attn_fwd_gqa(const void* q, const void* k, const void* v, voi
   DTD_LAUNCH_CHECK();
 }
 
+// Sliding-window forward (attn_fwd_win_kernel): dtd_attn_fwd_gqa with a causal window of `window`
+// keys per query.  1 <= Hkv <= H: with Hkv = H the q | k | v blocks of a multi-head qkv are this
+// layout with one query head per group.  The window travels in the argument block's p.
+template <int MODE>
+static void launch_fwd_win(int D, dim3 grid, hipStream_t s, const FwdArgs& a) {
+  if (D == 64) hipLaunchKernelGGL((attn_fwd_win_kernel<64, 3, 64, 1, MODE>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((attn_fwd_win_kernel<128, 1, 64, 2, MODE>), grid, dim3(256), 0, s, a);
+}
+static float window_bits(int window) {
+  float f;
+  memcpy(&f, &window, sizeof f);
+  return f;
+}
+DTD_EXPORT int dtd_attn_fwd_win(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H,
+                                int Hkv, int D, int ld, int ldo, int causal, float scale, int window,
+                                const int* kv_range, const int* doc, hipStream_t s) {
+  if (window <= 0 || !causal) return (int)hipErrorInvalidValue;
+  if (Hkv <= 0 || Hkv > H || H % Hkv) return (int)hipErrorInvalidValue;
+  if (kv_range && doc) return (int)hipErrorInvalidValue;
+  if (D != 64 && D != 128) return (int)hipErrorInvalidValue;
+  if (B * S * H == 0) return 0;
+  if (!offsets_fit(S, ld, ldo)) return (int)hipErrorInvalidValue;
+  const char* thr_env = getenv("DTD_ATTN_RESCALE_THR");
+  const float thr = thr_env ? (float)atof(thr_env) : kRescaleThr;
+  FwdArgs a{(const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, lse, nullptr, nullptr, nullptr, B, S, H, ld, ldo,
+            1, /*W = */ Hkv, scale, /*p = */ window_bits(window < S ? window : S), thr, doc ? doc : kv_range};
+  dim3 grid((S + 127) / 128, B * H);
+  if (doc) launch_fwd_win<2>(D, grid, s, a);
+  else if (kv_range) launch_fwd_win<1>(D, grid, s, a);
+  else launch_fwd_win<0>(D, grid, s, a);
+  DTD_LAUNCH_CHECK();
+}
+
 // 0 = the dQ + dK/dV pair, 1 = fused where it applies, 2 = fused, 4-wave form; returns the previous
 DTD_EXPORT int dtd_attn_fused_bwd_built() { return DTD_ATTN_FUSED_BWD; }
 
@@ -1718,6 +1795,38 @@ DTD_EXPORT int dtd_attn_bwd_gqa(const void* q, const void* k, const void* v, con
   if (doc) launch_bwd_gqa<2>(D, gq, gkv, s, a);
   else if (kv_range) launch_bwd_gqa<1>(D, gq, gkv, s, a);
   else launch_bwd_gqa<0>(D, gq, gkv, s, a);
+  DTD_LAUNCH_CHECK();
+}
+
+// Sliding-window backward (see dtd_attn_fwd_win): grids as in dtd_attn_bwd_gqa.
+template <int MODE>
+static void launch_bwd_win(int D, dim3 gq, dim3 gkv, hipStream_t s, const BwdArgs& a) {
+  const bool run_dq = g_bwd_kernels & 1, run_dkdv = g_bwd_kernels & 2;
+  if (D == 64) {
+    if (run_dq) hipLaunchKernelGGL((attn_bwd_dq_win_kernel<64, 3, 64, 1, MODE>), gq, dim3(256), 0, s, a);
+    if (run_dkdv) hipLaunchKernelGGL((attn_bwd_dkdv_win_kernel<64, 2, 128, MODE>), gkv, dim3(256), 0, s, a);
+  } else {
+    if (run_dq) hipLaunchKernelGGL((attn_bwd_dq_win_kernel<128, 1, 64, 2, MODE>), gq, dim3(256), 0, s, a);
+    if (run_dkdv) hipLaunchKernelGGL((attn_bwd_dkdv_win_kernel<128, 1, 64, MODE>), gkv, dim3(256), 0, s, a);
+  }
+}
+DTD_EXPORT int dtd_attn_bwd_win(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                                const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int S, int H,
+                                int Hkv, int D, int ld, int ldo, int causal, float scale, int window,
+                                const int* kv_range, const int* doc, hipStream_t s) {
+  if (window <= 0 || !causal) return (int)hipErrorInvalidValue;
+  if (Hkv <= 0 || Hkv > H || H % Hkv) return (int)hipErrorInvalidValue;
+  if (kv_range && doc) return (int)hipErrorInvalidValue;
+  if (D != 64 && D != 128) return (int)hipErrorInvalidValue;
+  if (B * S * H == 0) return 0;
+  if (!offsets_fit(S, ld, ldo)) return (int)hipErrorInvalidValue;
+  BwdArgs a{(const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)dout, lse, delta, (const bf16*)o,
+            (bf16*)dq, (bf16*)dk, (bf16*)dv, nullptr, nullptr, nullptr, B, S, H, ld, ldo, 1, /*W = */ Hkv, scale,
+            /*p = */ window_bits(window < S ? window : S), nullptr, doc ? doc : kv_range};
+  const dim3 gq((S + 127) / 128, B * H), gkv((S + 127) / 128, B * Hkv);
+  if (doc) launch_bwd_win<2>(D, gq, gkv, s, a);
+  else if (kv_range) launch_bwd_win<1>(D, gq, gkv, s, a);
+  else launch_bwd_win<0>(D, gq, gkv, s, a);
   DTD_LAUNCH_CHECK();
 }
 

@@ -1,5 +1,5 @@
 // Body of attn_bwd_dkdv_kernel / attn_bwd_dkdv_doc_kernel (attention.hip), included inside both (see
-// attention_fwd_body.h).  Expects D, OCC, BM, DROP, ALIBI, MASK, RANGE, DOC, GQA and the argument `a`.
+// attention_fwd_body.h).  Expects D, OCC, BM, DROP, ALIBI, MASK, RANGE, DOC, GQA, WIN and the argument `a`.
   static_assert(MASK || !(RANGE || DOC), "a key range needs the masked form");
   static_assert(!(RANGE && DOC), "a key range and document spans are exclusive");
   constexpr bool SWZ = D == 64;                 // swizzled unpadded image (swz64_off)
@@ -64,6 +64,13 @@
   const bool kin = key >= klo && key < khi;     // this lane's key takes part (RANGE)
   SpanOf<DOC> doc{};                            // this lane's key's document = its valid queries (DOC)
   if constexpr (DOC) doc = load_span(a.kv_range, b, S, key);
+  // WIN: key j is seen by the queries j <= q < j + win (the window rides in a.p, see
+  // attention_fwd_body.h); a span takes that end in
+  int win = 0;
+  if constexpr (WIN) {
+    win = __builtin_amdgcn_readfirstlane(__float_as_int(a.p));
+    if constexpr (DOC) doc.clip_hi(key + win);
+  }
   const float sl2 = a.slopes ? a.slopes[h] * kLog2e : 0.f;
   const float sc2 = a.scale * kLog2e;
   constexpr bool drop = DROP;
@@ -92,6 +99,7 @@
     qstart = (max(qstart, klo) / BM) * BM;
     qend = khi;
   }
+  if constexpr (WIN) qend = min(qend, kblk + 127 + win);   // the block's last key's last query, + 1
   const int nt = (qend - qstart + BM - 1) / BM;
   TileLoader<D, BM> ql, ol;
   // Raw lse / delta of a query tile, one row per thread of the first BM, issued straight behind the
@@ -184,6 +192,7 @@
       // block-uniform predicate (a scalar branch, never a per-element one)
       bool needmask = MASK && ((kblk + 128 > S) || (qrow0 + 32 > S) || (a.causal && kblk + 127 > qrow0));
       if constexpr (RANGE) needmask = needmask || kblk + 128 > khi || kblk < klo;   // the blocks holding lo / hi
+      if constexpr (WIN && !DOC) needmask = needmask || qrow0 + 31 - kblk >= win;   // the sub-block's last query is past the block's first key's window
       // (DOC: some key's span -- a pad's is empty -- leaves out some of the 32 queries; wave-uniform)
       if constexpr (DOC) needmask = !__all(doc.covers(qrow0, 32)) || (a.causal && kblk + 127 > qrow0);
       // this query block's keep masks (after the S / dP MFMAs consumed their LDS operands)
@@ -217,6 +226,7 @@
           const int qq = qrow0 + crow(i, hh);
           bool ok = kvalid && qq < S && !(a.causal && key > qq);
           if constexpr (RANGE) ok = ok && kin;
+          if constexpr (WIN) ok = ok && qq < key + win;
           if constexpr (DOC) ok = doc.has(qq) && !(a.causal && key > qq);   // (the span lies inside [0, S))
           sacc[i] = ok ? sacc[i] : 0.f;
         }

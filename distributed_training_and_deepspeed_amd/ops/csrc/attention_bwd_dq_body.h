@@ -1,7 +1,7 @@
 // Body of attn_bwd_dq_kernel / attn_bwd_dq_doc_kernel (attention.hip), included inside both (see
-// attention_fwd_body.h).  Expects D, OCC, BN, RING, PK, RANGE, DOC, GQA and the argument `a`.
+// attention_fwd_body.h).  Expects D, OCC, BN, RING, PK, RANGE, DOC, GQA, WIN and the argument `a`.
   static_assert(!(RANGE && DOC), "a key range and document spans are exclusive");
-  constexpr bool RNG = RANGE || DOC;
+  constexpr bool RNG = RANGE || DOC || WIN;
   constexpr bool SWZ = D == 64;                 // swizzled unpadded K / V images (swz64_off)
   constexpr int KP = SWZ ? D : D + 8, NC = D / 16, NDB = D / 32;
   __shared__ __attribute__((aligned(16))) bf16 Ks[2][BN * KP];
@@ -40,6 +40,12 @@
   if constexpr (DOC) {
     load_block_range(a.kv_range, a.B, b, gridDim.x, tx, S, klo, khi);
     doc = load_span(a.kv_range, b, S, q);
+  }
+  int win = 0;   // WIN: the sliding window, folded into the tile range and the span as in attn_fwd_kernel
+  if constexpr (WIN) {
+    win = __builtin_amdgcn_readfirstlane(__float_as_int(a.p));
+    klo = max(klo, qblk - win + 1);
+    if constexpr (DOC) doc.clip_lo(q - win + 1);
   }
   const int kend = a.causal ? min(khi, qblk + 128) : khi;
   const int nt = (kend + BN - 1) / BN;
@@ -106,6 +112,7 @@
     const bf16* K = Ks[buf];
     const bf16* V = Vs[buf];
     bool needmask = !qvalid || (k0 + BN > khi) || (RANGE && k0 < klo) || (a.causal && k0 + BN - 1 > q0);
+    if constexpr (WIN && !DOC) needmask = needmask || k0 + win <= q0 + 31;
     // (DOC: a wave-uniform vote; a row past S has an empty span)
     if constexpr (DOC) needmask = !__all(doc.covers(k0, BN)) || (a.causal && k0 + BN - 1 > q0);
 #pragma unroll
@@ -137,7 +144,7 @@
           if constexpr (DOC) {
             if (needmask && (!doc.has(key) || (a.causal && key > q))) pv = 0.f;
           } else {
-            if (needmask && (!qvalid || key >= khi || (RANGE && key < klo) || (a.causal && key > q))) pv = 0.f;
+            if (needmask && (!qvalid || key >= khi || (RANGE && key < klo) || (a.causal && key > q) || (WIN && key + win <= q))) pv = 0.f;
           }
           sacc[i] = pv;
         }

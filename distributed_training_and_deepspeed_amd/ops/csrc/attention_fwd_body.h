@@ -1,9 +1,9 @@
 // Body of attn_fwd_kernel / attn_fwd_doc_kernel (attention.hip), included inside both: a shared
 // __device__ function, inlined, did not leave the existing instantiations' registers as they were.
 // Expects the template parameters D, OCC, BN, RING and the constants PK, RANGE, DOC, GQA in scope, and
-// the kernel argument `a`.
+// the kernel argument `a`.  WIN (attn_fwd_win_kernel): a causal sliding window of `win` keys per query.
   static_assert(!(RANGE && DOC), "a key range and document spans are exclusive");
-  constexpr bool RNG = RANGE || DOC;            // a tile range [t0, nt) that need not start at 0
+  constexpr bool RNG = RANGE || DOC || WIN;     // a tile range [t0, nt) that need not start at 0
   // K rows (ds_read_b128, 4x16-lane groups): pitch D+8 puts the 16 rows of a group on 16
   // distinct 4-bank windows.  V (ds_read_b64_tr_b16, rows rr = 0..3 x column halves g = 0,1 per
   // 32-lane group): pitch D+32 (48 / 80 dwords = 16 mod 64) places the eight 8-dword windows
@@ -59,6 +59,15 @@
   if constexpr (DOC) {
     load_block_range(a.kv_range, a.B, b, gridDim.x, tx, S, klo, khi);
     doc = load_span(a.kv_range, b, S, q);
+  }
+  // WIN: query q sees key j iff q - win < j <= q (the windowed forms run causal, without dropout, so
+  // the argument block's p carries the window as an integer).  The block's first key is that of its
+  // first query, so the tile range starts there; a span takes the window in at no cost.
+  int win = 0;
+  if constexpr (WIN) {
+    win = __builtin_amdgcn_readfirstlane(__float_as_int(a.p));
+    klo = max(klo, qblk - win + 1);
+    if constexpr (DOC) doc.clip_lo(q - win + 1);
   }
   const int kend = a.causal ? min(khi, qblk + 128) : khi;
   const int nt = (kend + BN - 1) / BN;
@@ -126,6 +135,8 @@
     // incl. the running sum, vs 10+ with a per-element scale/bias/mask pass.
     // (RANGE: khi <= S stands for the end of the keys, and the tile holding klo is masked too)
     bool needmask = (k0 + BN > khi) || (RANGE && k0 < klo) || (a.causal && k0 + BN - 1 > q0);
+    // (WIN: the wave's last query no longer sees the tile's first key)
+    if constexpr (WIN && !DOC) needmask = needmask || k0 + win <= q0 + 31;
     // (DOC: some lane's span -- a pad's is empty -- leaves part of the tile out)
     if constexpr (DOC) needmask = !__all(doc.covers(k0, BN)) || (a.causal && k0 + BN - 1 > q0);
     const bool slow = needmask || sl2 != 0.f;
@@ -140,7 +151,7 @@
           if constexpr (DOC) {
             if (needmask && (!doc.has(key) || (a.causal && key > q))) s = -INFINITY;
           } else {
-            if (needmask && (key >= khi || (RANGE && key < klo) || (a.causal && key > q))) s = -INFINITY;
+            if (needmask && (key >= khi || (RANGE && key < klo) || (a.causal && key > q) || (WIN && key + win <= q))) s = -INFINITY;
           }
           sacc[kb][i] = s;
           tmax = fmaxf(tmax, s);
