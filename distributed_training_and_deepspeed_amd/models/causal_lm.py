@@ -11,7 +11,11 @@ gpt2-medium.  SURVEY.md D17:
   * Llama (models/llama.py): word embeddings only, RMSNorm blocks with rotary q / k and a SwiGLU MLP, no
     biases, final RMSNorm, untied head.  Rotary positions are arange(S), also under ``attention_mask``
     (as HF's; rotary attention depends only on position differences), and restart at each document
-    with ``segment_ids``.
+    with ``segment_ids``;
+  * Mixtral (models/moe.py, ``cfg.num_experts > 0``): the Llama layer with a routed mixture-of-experts FFN.
+    ``loss`` then includes ``cfg.router_aux_loss_coef * aux_loss``, ``aux_loss`` being the mean over the layers
+    of their load-balancing losses (every position counts, pads included); ``output_router_logits=True`` also
+    returns each layer's [T, E] router logits (HF's name).
 Loss: shifted next-token cross entropy (labels = input_ids, ignore_index -100).
 
 ``forward(..., attention_mask=...)`` takes HF's 0/1 ``[B, S]`` key-padding mask (contiguous: left-
@@ -38,6 +42,7 @@ from torch import nn
 from .config import BLOOM_560M, TransformerConfig, get_config
 from .layers import Embeddings, LayerNorm, LMHead, RMSNorm
 from .llama import LlamaLayer
+from .moe import MoeLlamaLayer
 from ..ops.attention import doc_position_ids, doc_range_from_segment_ids, key_range_from_mask
 from .transformer import Runtime, TransformerLayer, prefetch_masks, stage_dgrad_transposes
 
@@ -46,6 +51,8 @@ from .transformer import Runtime, TransformerLayer, prefetch_masks, stage_dgrad_
 class CausalLMOutput:
     loss: torch.Tensor | None = None
     logits: torch.Tensor | None = None
+    aux_loss: torch.Tensor | None = None          # mixture-of-experts models: mean load-balancing loss of the layers
+    router_logits: tuple | None = None            # with output_router_logits: one [T, E] tensor per layer
 
 
 class CausalLM(nn.Module):
@@ -54,7 +61,7 @@ class CausalLM(nn.Module):
         self.config = self.cfg = cfg
         self.rt = rt or Runtime()
         self.embeddings = Embeddings(cfg, self.rt)
-        layer_cls = LlamaLayer if cfg.llama_style else TransformerLayer
+        layer_cls = (MoeLlamaLayer if cfg.num_experts else LlamaLayer) if cfg.llama_style else TransformerLayer
         norm_cls = RMSNorm if cfg.norm == "rms" else LayerNorm
         self.layers = nn.ModuleList([layer_cls(cfg, self.rt) for _ in range(cfg.num_layers)])
         self.final_ln = norm_cls(cfg.hidden_size, cfg.ln_eps, self.rt) if cfg.final_ln else None
@@ -108,11 +115,17 @@ class CausalLM(nn.Module):
 
     def forward(self, input_ids: torch.Tensor, labels: torch.Tensor | None = None,
                 return_logits: bool = False, attention_mask: torch.Tensor | None = None,
-                segment_ids: torch.Tensor | None = None) -> CausalLMOutput:
+                segment_ids: torch.Tensor | None = None, output_router_logits: bool = False) -> CausalLMOutput:
         x = self.encode(input_ids, attention_mask, segment_ids)
         out = CausalLMOutput()
         if labels is not None:
             out.loss = self.head(x, labels)
+        if self.cfg.num_experts:
+            out.aux_loss = torch.stack([layer.aux_loss for layer in self.layers]).mean()
+            if out.loss is not None and self.cfg.router_aux_loss_coef:
+                out.loss = out.loss + self.cfg.router_aux_loss_coef * out.aux_loss
+            if output_router_logits:
+                out.router_logits = tuple(layer.router_logits for layer in self.layers)
         if labels is None or return_logits:
             out.logits = self.head.logits(x)
         return out

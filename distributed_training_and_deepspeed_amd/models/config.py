@@ -44,6 +44,10 @@ class TransformerConfig:
     rope_theta: float = 0.0           # rotary position embedding base; 0 = off
     num_kv_heads: int = 0             # grouped-query attention (Llama family): key/value heads; 0 = num_heads
     sliding_window: int = 0           # causal sliding-window attention (Mistral): keys per query, own included; 0 = off
+    num_experts: int = 0              # mixture-of-experts FFN (Mixtral, models/moe.py): experts per layer; 0 = dense
+    experts_per_token: int = 2        # experts each token is routed to (top-k)
+    moe_capacity_factor: float = 0.0  # slots per expert = cf * T * k / E, rounded up to 8 (DeepSpeed); 0.0 = dropless
+    router_aux_loss_coef: float = 0.0  # weight of the load-balancing loss in the model's loss
     # activation "swiglu": the gated MLP down(silu(gate(x)) * up(x)), three weights, no bias
 
     def __post_init__(self):
@@ -75,6 +79,17 @@ class TransformerConfig:
         if self.sliding_window and not (self.llama_style and self.causal and self.attn_dropout == 0):
             raise ValueError("a sliding window (sliding_window > 0) is implemented by models/llama.py::LlamaLayer "
                              "only, for causal models without attention dropout")
+
+        if self.num_experts < 0:
+            raise ValueError(f"num_experts = {self.num_experts} must be >= 0 (0 = dense)")
+        if self.num_experts and not self.llama_style:
+            raise ValueError("a mixture-of-experts FFN (num_experts > 0) is implemented by models/moe.py::MoeLlamaLayer "
+                             "only, for the Llama family")
+        if self.num_experts and not 1 <= self.experts_per_token <= self.num_experts:
+            raise ValueError(f"experts_per_token = {self.experts_per_token} must be in [1, num_experts = "
+                             f"{self.num_experts}]")
+        if self.moe_capacity_factor < 0:
+            raise ValueError(f"moe_capacity_factor = {self.moe_capacity_factor} must be >= 0 (0 = dropless)")
 
     @property
     def kv_heads(self) -> int:
@@ -143,7 +158,8 @@ CAUSAL_TINY = GPT2_MEDIUM.with_(name="causal-tiny", vocab_size=1024, hidden_size
 # Llama family (HF LlamaForCausalLM): RMSNorm, rotary embeddings, SwiGLU MLP, no biases, no position
 # table, untied head.  num_kv_heads < num_heads: grouped-query attention (TinyLlama, Llama-3).  Parameter
 # counts (tests/test_llama_cpu.py, tests/test_gqa_cpu.py): 2 V h + L (2 h^2 + 2 h Hkv D + 3 h f + 2 h) + h,
-# with Hkv D = h for multi-head attention.  Mistral is a grouped-query Llama with sliding_window keys per
+# with Hkv D = h for multi-head attention; with E experts (Mixtral, below) the FFN term L 3 h f becomes
+# L (E 3 h f + E h): E expert FFNs and the [E, h] router.  Mistral is a grouped-query Llama with sliding_window keys per
 # query (HF MistralForCausalLM; the tensor names are Llama's).  Llama-3.1 / 3.2 (rotary scaling) are not
 # described here.
 LLAMA_160M = TransformerConfig(
@@ -170,12 +186,20 @@ LLAMA_TINY_GQA = LLAMA_160M.with_(name="llama-tiny-gqa", vocab_size=1024, hidden
 MISTRAL_7B = LLAMA_160M.with_(name="mistralai/Mistral-7B-v0.1", hidden_size=4096, num_layers=32, num_heads=32,
                               num_kv_heads=8, ffn_size=14336, max_positions=32768, ln_eps=1e-5, sliding_window=4096)
 MISTRAL_TINY = LLAMA_TINY_GQA.with_(name="mistral-tiny", sliding_window=48)
+# mixture of experts (HF MixtralForCausalLM): Mistral's attention without the window, E SwiGLU experts per
+# layer, k of them per token.  mixtral-8x7b (46,702,792,704 parameters) is described and counted, not trained
+# on one card.
+MIXTRAL_8X7B = MISTRAL_7B.with_(name="mistralai/Mixtral-8x7B-v0.1", sliding_window=0, rope_theta=1e6, num_experts=8,
+                                experts_per_token=2, router_aux_loss_coef=0.02)
+MOE_8X160M = LLAMA_160M.with_(name="moe-8x160m", num_experts=8, experts_per_token=2, router_aux_loss_coef=0.02)
+MIXTRAL_TINY = LLAMA_TINY_GQA.with_(name="mixtral-tiny", num_experts=4, experts_per_token=2,
+                                    router_aux_loss_coef=0.02)
 
 PRESETS = {
     c.name: c
     for c in (BERT_BASE, BERT_LARGE, BERT_TINY, BLOOM_560M, OPT_125M, GPT2_MEDIUM, W4_BLOCK,
               CAUSAL_TINY, LLAMA_160M, SHEARED_LLAMA_1_3B, LLAMA_2_7B, LLAMA_TINY, TINYLLAMA_1_1B, LLAMA_3_8B,
-              LLAMA_TINY_GQA, MISTRAL_7B, MISTRAL_TINY)
+              LLAMA_TINY_GQA, MISTRAL_7B, MISTRAL_TINY, MIXTRAL_8X7B, MOE_8X160M, MIXTRAL_TINY)
 }
 ALIASES = {
     "base": "bert-base-cased", "large": "bert-large-cased", "tiny": "bert-tiny",
@@ -185,7 +209,7 @@ ALIASES = {
     "llama-160m": "JackFram/llama-160m", "sheared-llama-1.3b": "princeton-nlp/Sheared-LLaMA-1.3B",
     "llama-2-7b": "meta-llama/Llama-2-7b-hf",
     "tinyllama-1.1b": "TinyLlama/TinyLlama_v1.1", "llama-3-8b": "meta-llama/Meta-Llama-3-8B",
-    "mistral-7b": "mistralai/Mistral-7B-v0.1",
+    "mistral-7b": "mistralai/Mistral-7B-v0.1", "mixtral-8x7b": "mistralai/Mixtral-8x7B-v0.1",
 }
 
 

@@ -258,7 +258,12 @@ def from_hf_state_dict(sd: dict) -> dict:
     simply have fewer rows.  ``rotary_emb.inv_freq`` buffers of older checkpoints are dropped; a tied
     checkpoint (no ``lm_head.weight``) gets the embedding table.  An HF ``MistralForCausalLM`` state dict
     converts unchanged, here and in ``to_hf_state_dict``: its tensor names are Llama's, and the sliding
-    window is a matter of the config (``sliding_window``), not of the weights."""
+    window is a matter of the config (``sliding_window``), not of the weights.
+
+    An HF ``MixtralForCausalLM`` state dict (models/moe.py) converts too: ``mlp.gate.weight [E, h]``,
+    ``mlp.experts.gate_up_proj [E, 2f, h]`` and ``mlp.experts.down_proj [E, h, f]`` map one to one onto gate_w,
+    gu_w and down_w; the older per-expert names ``block_sparse_moe.gate.weight`` and
+    ``block_sparse_moe.experts.J.w1 / w3 / w2.weight`` (gate / up / down) are stacked into the same tensors."""
     out = {"embeddings.word": sd["model.embed_tokens.weight"],
            "final_ln.weight": sd["model.norm.weight"],
            "head.own_weight": sd["lm_head.weight"] if "lm_head.weight" in sd else sd["model.embed_tokens.weight"]}
@@ -269,8 +274,19 @@ def from_hf_state_dict(sd: dict) -> dict:
         out[q + "qkv_w"] = torch.cat([sd[att + "q_proj.weight"], sd[att + "k_proj.weight"], sd[att + "v_proj.weight"]], 0)
         out[q + "o_w"] = sd[att + "o_proj.weight"]
         out[q + "n1_g"] = sd[p + "input_layernorm.weight"]
-        out[q + "gu_w"] = torch.cat([sd[mlp + "gate_proj.weight"], sd[mlp + "up_proj.weight"]], 0)
-        out[q + "down_w"] = sd[mlp + "down_proj.weight"]
+        old = p + "block_sparse_moe."
+        if mlp + "experts.gate_up_proj" in sd:         # Mixtral, fused expert tensors
+            out[q + "gate_w"] = sd[mlp + "gate.weight"]
+            out[q + "gu_w"] = sd[mlp + "experts.gate_up_proj"]
+            out[q + "down_w"] = sd[mlp + "experts.down_proj"]
+        elif old + "gate.weight" in sd:                # Mixtral, one w1 (gate) / w3 (up) / w2 (down) per expert
+            out[q + "gate_w"] = sd[old + "gate.weight"]
+            ex = [old + f"experts.{j}." for j in range(out[q + "gate_w"].shape[0])]
+            out[q + "gu_w"] = torch.stack([torch.cat([sd[e + "w1.weight"], sd[e + "w3.weight"]], 0) for e in ex])
+            out[q + "down_w"] = torch.stack([sd[e + "w2.weight"] for e in ex])
+        else:
+            out[q + "gu_w"] = torch.cat([sd[mlp + "gate_proj.weight"], sd[mlp + "up_proj.weight"]], 0)
+            out[q + "down_w"] = sd[mlp + "down_proj.weight"]
         out[q + "n2_g"] = sd[p + "post_attention_layernorm.weight"]
         if sd[att + "q_proj.weight"].shape[0] != out[q + "o_w"].shape[0] \
                 or sd[att + "k_proj.weight"].shape[0] != sd[att + "v_proj.weight"].shape[0]:
@@ -284,7 +300,8 @@ def from_hf_state_dict(sd: dict) -> dict:
 def to_hf_state_dict(sd: dict) -> dict:
     """The inverse of ``from_hf_state_dict``: split qkv_w into q/k/v and gu_w into gate/up.  The split
     goes by sizes, so no config is needed: the q rows are as many as ``o_w``'s, the rest halves into k
-    and v (fewer rows than q with grouped-query attention)."""
+    and v (fewer rows than q with grouped-query attention).  A mixture-of-experts layer (it has a ``gate_w``)
+    is written under HF 5's fused Mixtral names."""
     out = {"model.embed_tokens.weight": sd["embeddings.word"], "model.norm.weight": sd["final_ln.weight"],
            "lm_head.weight": sd["head.own_weight"]}
     i = 0
@@ -294,12 +311,16 @@ def to_hf_state_dict(sd: dict) -> dict:
         nq = sd[q + "o_w"].shape[0]
         nkv = (sd[q + "qkv_w"].shape[0] - nq) // 2
         qw, kw, vw = sd[q + "qkv_w"].split([nq, nkv, nkv], 0)
-        gw, uw = sd[q + "gu_w"].chunk(2, 0)
+        if q + "gate_w" in sd:
+            out[mlp + "gate.weight"] = sd[q + "gate_w"]
+            out[mlp + "experts.gate_up_proj"], out[mlp + "experts.down_proj"] = sd[q + "gu_w"], sd[q + "down_w"]
+        else:
+            gw, uw = sd[q + "gu_w"].chunk(2, 0)
+            out[mlp + "gate_proj.weight"], out[mlp + "up_proj.weight"] = gw, uw
+            out[mlp + "down_proj.weight"] = sd[q + "down_w"]
         out[att + "q_proj.weight"], out[att + "k_proj.weight"], out[att + "v_proj.weight"] = qw, kw, vw
         out[att + "o_proj.weight"] = sd[q + "o_w"]
         out[p + "input_layernorm.weight"] = sd[q + "n1_g"]
-        out[mlp + "gate_proj.weight"], out[mlp + "up_proj.weight"] = gw, uw
-        out[mlp + "down_proj.weight"] = sd[q + "down_w"]
         out[p + "post_attention_layernorm.weight"] = sd[q + "n2_g"]
         i += 1
     return out

@@ -23,6 +23,9 @@ values, quirk 12).
                                    # llama-tiny-gqa
   python zero_dp_training.py --stage 0 --model-name mistralai/Mistral-7B-v0.1     # sliding-window attention (4096 keys):
                                    # also mistral-tiny (48); --sliding-window N gives any Llama-family preset a window
+  python zero_dp_training.py --stage 0 --model-name moe-8x160m --impl reference --moe-capacity-factor 1.0
+                                   # mixture of experts (models/moe.py, reference implementation only): also
+                                   # mixtral-tiny, mistralai/Mixtral-8x7B-v0.1; without the flag dropless
 """
 import argparse
 import json
@@ -69,8 +72,30 @@ def window_config(model_name, sliding_window: int):
     return cfg.with_(sliding_window=sliding_window)
 
 
+def moe_config(model_name, capacity_factor):
+    """The model to train: ``model_name`` (a preset's name or a config), or with ``--moe-capacity-factor F`` its
+    config with that capacity factor -- for a mixture-of-experts preset only (``ValueError`` otherwise).  F = 0
+    is the dropless mode."""
+    if capacity_factor is None:
+        return model_name
+    cfg = get_config(model_name)
+    if capacity_factor < 0 or not cfg.num_experts:
+        raise ValueError(f"--moe-capacity-factor takes a factor >= 0 and a mixture-of-experts model "
+                         f"(models/moe.py implements it), got {capacity_factor} for {cfg.name} (dense)")
+    return cfg.with_(moe_capacity_factor=float(capacity_factor))
+
+
+def moe_impl_check(model_name, impl: str, cuda: bool) -> None:
+    """A mixture-of-experts model has the reference implementation only (models/moe.py): the fused one -- asked
+    for by name, or chosen by 'auto' on a GPU -- is a ``ValueError`` here, before anything is built."""
+    if get_config(model_name).num_experts and (impl == "fused" or (impl == "auto" and cuda)):
+        raise ValueError("mixture-of-experts models have no fused implementation yet: pass --impl reference")
+
+
 def train(model_name, batch_size, training_steps, stage, opts):
     model_name = window_config(model_name, getattr(opts, "sliding_window", 0))
+    model_name = moe_config(model_name, getattr(opts, "moe_capacity_factor", None))
+    moe_impl_check(model_name, opts.impl, (opts.backend or ("nccl" if torch.cuda.is_available() else "gloo")) == "nccl")
     rank = int(os.getenv("LOCAL_RANK", "0"))
     world_size = int(os.getenv("WORLD_SIZE", "1"))
     backend = opts.backend or ("nccl" if torch.cuda.is_available() else "gloo")
@@ -152,8 +177,11 @@ def train(model_name, batch_size, training_steps, stage, opts):
             outputs = model_engine(input_ids, labels=labels, attention_mask=attention_mask)
         model_engine.backward(outputs.loss)
         model_engine.step()
+        if getattr(outputs, "aux_loss", None) is not None:
+            aux_loss[:] = [outputs.aux_loss.detach()]   # under --graph a static tensor every replay rewrites
         return outputs.loss.detach()
 
+    aux_loss = []      # mixture-of-experts models: the last step's load-balancing loss
     graphed, batches, warm = None, iter(loader), []
     if graph:
         # whole step (forward, backward + gradient reduction, fused Adam, parameter refresh,
@@ -204,7 +232,8 @@ def train(model_name, batch_size, training_steps, stage, opts):
         print(json.dumps({"tokens_per_s": round(tokens / max(elapsed, 1e-9), 1),
                           "labelled_tokens_per_s": round(labelled * tokens / max(elapsed, 1e-9), 1), "stage": stage,
                           "partition_numel": model_engine.partition_numel(),
-                          "final_loss": round(float(loss.detach()), 4), "hip_graph": graphed is not None}))
+                          "final_loss": round(float(loss.detach()), 4), "hip_graph": graphed is not None,
+                          **({"aux_loss": round(float(aux_loss[0]), 4)} if aux_loss else {})}))
     comm.destroy()
 
 
@@ -244,12 +273,16 @@ if __name__ == "__main__":
     parser.add_argument("--sliding-window", type=int, default=0, metavar="N",
                         help="Llama family: causal sliding-window attention over N keys per query, overriding "
                              "the preset's window (0 = keep the preset's, e.g. mistral-tiny's 48)")
+    parser.add_argument("--moe-capacity-factor", type=float, default=None, metavar="F",
+                        help="mixture-of-experts models: slots per expert = F * tokens * k / experts (rounded up to "
+                             "8), pairs past them are dropped; 0 = dropless (default: the preset's)")
     parser.add_argument("--quiet", action="store_true")
     args, extra_args = parser.parse_known_args()
     if args.pack_docs and args.attention_mask:
         parser.error("--pack-docs and --attention-mask are mutually exclusive (segment id 0 marks the padding)")
     try:
-        window_config(args.model_name, args.sliding_window)
+        moe_config(window_config(args.model_name, args.sliding_window), args.moe_capacity_factor)
+        moe_impl_check(args.model_name, args.impl, (args.backend or ("nccl" if torch.cuda.is_available() else "gloo")) == "nccl")
     except ValueError as e:
         parser.error(str(e))
     if args.num_gpus and "WORLD_SIZE" not in os.environ:
