@@ -99,18 +99,6 @@ def _split_gqa(qkv, B, S, H, Hkv, D):
     return (x[:, :, :H].transpose(1, 2), x[:, :, H:H + Hkv].transpose(1, 2), x[:, :, H + Hkv:].transpose(1, 2))
 
 
-def _gqa_entry(name: str) -> str:
-    if not _lib.has(name):
-        raise _lib.KernelError("the kernel library has no grouped-query attention entry points (stale build)")
-    return name
-
-
-def _win_entry(name: str) -> str:
-    if not _lib.has(name):
-        raise _lib.KernelError("the kernel library has no sliding-window attention entry points (stale build)")
-    return name
-
-
 def _window(window, S: int, causal, p, slopes) -> int:
     """The effective window of a call: 0 = none (None, 0, or >= S, where the band is the whole causal
     triangle); otherwise validated (module docstring)."""
@@ -388,12 +376,18 @@ def fused_bwd_applies(S: int, D: int, causal: bool, slopes, key_range=None, doc_
             and fused_bwd_built())
 
 
+def _require(name: str, what: str) -> str:
+    """Entry point ``name`` of the kernel library; one built before it existed is an error, not a fallback."""
+    if not _lib.has(name):
+        raise _lib.KernelError(f"the kernel library has no {what} attention entry points (stale build)")
+    return name
+
+
 def _range_arg(key_range: torch.Tensor, B: int, device) -> torch.Tensor:
     """The kernels' kv_range argument: int32 [B, 2], contiguous, on the activations' device."""
     if tuple(key_range.shape) != (B, 2):
         raise ValueError(f"key_range must be [B, 2] = [{B}, 2], got {tuple(key_range.shape)}")
-    if not _lib.has("dtd_attn_fwd_range"):
-        raise _lib.KernelError("the kernel library has no ranged attention entry points (stale build)")
+    _require("dtd_attn_fwd_range", "ranged")
     return key_range.to(device=device, dtype=torch.int32).contiguous()
 
 
@@ -401,8 +395,7 @@ def _doc_arg(doc_range, B: int, S: int, device) -> torch.Tensor:
     """The kernels' doc argument: int32, the [B, S, 2] spans then the [B, ceil(S/128), 2] block
     bounds, contiguous, on the activations' device.  Bare [B, S, 2] spans get their bounds here."""
     _doc_ranges(doc_range, B, S)
-    if not _lib.has("dtd_attn_fwd_doc"):
-        raise _lib.KernelError("the kernel library has no document-masked attention entry points (stale build)")
+    _require("dtd_attn_fwd_doc", "document-masked")
     if not isinstance(doc_range, DocRange):
         doc_range = _doc_pack(doc_range.to(device))
     flat = doc_range.flat.to(device=device, dtype=torch.int32).contiguous()
@@ -508,6 +501,75 @@ def attn_masks_async(B, S, H, D, p, rng: RngState, sid, device) -> PendingMasks 
     return PendingMasks(masks, ev)
 
 
+class _Route(NamedTuple):
+    """Where a call runs: the math ``reference``, or a kernel family -- ``f32`` (reference-precision),
+    ``mha`` (bf16 multi-head), ``gqa``, ``win`` -- with the validated Hkv and effective window."""
+    family: str
+    Hkv: int
+    window: int
+
+
+# (forward, backward) entry points of the kernel families; mha by key_range / doc_range
+_ENTRY = {
+    "f32": ("dtd_attn_fwd_f32", "dtd_attn_bwd_f32"),
+    "mha": ("dtd_attn_fwd", "dtd_attn_bwd"),
+    "mha_range": ("dtd_attn_fwd_range", "dtd_attn_bwd_range"),
+    "mha_doc": ("dtd_attn_fwd_doc", "dtd_attn_bwd_doc"),
+    "gqa": ("dtd_attn_fwd_gqa", "dtd_attn_bwd_gqa"),
+    "win": ("dtd_attn_fwd_win", "dtd_attn_bwd_win"),
+}
+
+
+def _route(qkv, B, S, H, D, causal, slopes, p, key_range, doc_range, kv_heads, window, backward: bool,
+           masks=None) -> _Route:
+    """The one routing rule of ``attn_fwd`` and ``attn_bwd`` (``backward``), so that a backward takes
+    its forward's family.  A window, then grouped-query heads: bf16 on the GPU with D 64 / 128 runs
+    their kernels (a library without them is an error, not a fallback), everything else the math
+    reference.  Multi-head: fp32 with a range or spans takes the reference (the fp32 kernels know
+    neither), other fp32 the fp32 kernels (a backward with dropout only given the keep bits), bf16 the
+    bf16 kernels; a GPU build without them warns once and falls back."""
+    _exclusive(key_range, doc_range)
+    Hkv = _kv_heads(kv_heads, H)
+    window = _window(window, S, causal, p, slopes)
+    family = "reference"
+    if window or Hkv != H:
+        _check_gqa(qkv, B, S, H, Hkv, D, p, slopes)     # (a window: p = 0 and no slopes here -- the width)
+        if qkv.is_cuda and qkv.dtype == torch.bfloat16 and D in (64, 128):
+            family = "win" if window else "gqa"
+            _require(_ENTRY[family][backward], "sliding-window" if window else "grouped-query")
+    elif qkv.dtype == torch.float32 and (key_range is not None or doc_range is not None):
+        pass
+    elif f32_kernel_supported(qkv, D) and (not backward or p <= 0 or masks is not None):
+        family = "f32"
+    elif kernel_supported(qkv, D):
+        family = "mha"
+    elif not backward and qkv.is_cuda and qkv.dtype == torch.bfloat16 and _lib.has("dtd_attn_fwd") is False:
+        _warn_once()
+    return _Route(family, Hkv, window)
+
+
+def _views(t: torch.Tensor, H: int, Hkv: int, D: int):
+    """(q, k, v, ld): the addresses of the q | k | v blocks (H, Hkv and Hkv heads of D columns) inside
+    the first row of a packed qkv / dqkv, and its row stride in elements.  Hkv = H is [.., 3, H, D]."""
+    base, es = t.data_ptr(), t.element_size()
+    return base, base + H * D * es, base + (H + Hkv) * D * es, (H + 2 * Hkv) * D
+
+
+def _range_ptrs(r: _Route, key_range, doc_range, B, S, device, backward: bool):
+    """(entry point, its key-range / document arguments, the tensors to keep alive) of a bf16 call:
+    the grouped families take both pointers, either may be null; the multi-head entries are one per
+    kind of masking and take their own."""
+    kr = _range_arg(key_range, B, device) if key_range is not None else None
+    doc = _doc_arg(doc_range, B, S, device) if doc_range is not None else None
+    if r.family != "mha":
+        return _ENTRY[r.family][backward], (_lib.ptr(kr), _lib.ptr(doc)), (kr, doc)
+    if doc is not None:
+        return _ENTRY["mha_doc"][backward], (doc.data_ptr(),), doc
+    if kr is not None:
+        return _ENTRY["mha_range"][backward], (kr.data_ptr(),), kr
+    return _ENTRY["mha"][backward], (), None
+
+
 def attn_fwd(qkv, B, S, H, D, causal=False, slopes=None, p=0.0, rng: RngState | None = None, sid=0,
              masks: PendingMasks | None = None, key_range: torch.Tensor | None = None,
              doc_range: DocRange | torch.Tensor | None = None, kv_heads: int | None = None,
@@ -531,52 +593,41 @@ def attn_fwd(qkv, B, S, H, D, causal=False, slopes=None, p=0.0, rng: RngState | 
     ``window``: causal sliding window of that many keys per query (module docstring).  The bf16
     kernels visit only the band's key tiles; fp32 and CPU inputs take the math reference.  None, 0 or
     >= S: exactly the call without the argument."""
-    _exclusive(key_range, doc_range)
-    Hkv = _kv_heads(kv_heads, H)
-    window = _window(window, S, causal, p, slopes)
-    if window:       # (p = 0 here, so there are no keep bits to join)
-        return _attn_fwd_win(qkv, B, S, H, Hkv, D, window, key_range, doc_range)
-    if Hkv != H:
-        return _attn_fwd_gqa(qkv, B, S, H, Hkv, D, causal, slopes, p, key_range, doc_range)
-    if (key_range is not None or doc_range is not None) and qkv.dtype == torch.float32:
+    r = _route(qkv, B, S, H, D, causal, slopes, p, key_range, doc_range, kv_heads, window, False)
+    if r.family == "reference":
         if masks is not None:    # keep bits generated ahead for the fp32 kernels: unused, but join
             torch.cuda.current_stream(qkv.device).wait_event(masks.event)   # before their buffer is freed
-        ctx, lse = attn_fwd_ref(qkv, B, S, H, D, causal, slopes, p, rng, sid, key_range=key_range, doc_range=doc_range)
-        return ctx, lse, None
-    if f32_kernel_supported(qkv, D):
-        return _attn_fwd_f32(qkv, B, S, H, D, causal, slopes, p, rng, sid, masks)
-    if not kernel_supported(qkv, D):
-        if qkv.is_cuda and qkv.dtype == torch.bfloat16 and _lib.has("dtd_attn_fwd") is False:
-            _warn_once()
-        ctx, lse = attn_fwd_ref(qkv, B, S, H, D, causal, slopes, p, rng, sid, key_range=key_range, doc_range=doc_range)
+        ctx, lse = attn_fwd_ref(qkv, B, S, H, D, causal, slopes, p, rng, sid, key_range=key_range, doc_range=doc_range,
+                                kv_heads=r.Hkv, window=r.window)
         return ctx, lse, None
     qkv = qkv.contiguous()
     ctx = torch.empty((B * S, H * D), dtype=qkv.dtype, device=qkv.device)
     lse = torch.empty((B, H, S), dtype=torch.float32, device=qkv.device)
+    q, k, v, ld = _views(qkv, H, r.Hkv, D)
+    scale = 1.0 / math.sqrt(D)
+    if r.family in ("gqa", "win"):       # (no dropout, so no keep bits; causal = 1 under a window)
+        name, ranges, _keep = _range_ptrs(r, key_range, doc_range, B, S, qkv.device, False)
+        win = (1, scale, r.window) if r.window else (int(causal), scale)
+        _lib.call(name, q, k, v, ctx.data_ptr(), lse.data_ptr(), B, S, H, r.Hkv, D, ld, H * D, *win, *ranges, _lib.stream())
+        return ctx, lse, None
     rng_ptr = rng.state.data_ptr() if rng is not None else None
     if p > 0 and masks is not None:
         torch.cuda.current_stream(qkv.device).wait_event(masks.event)
         masks, rng_ptr = masks.masks, None     # generated already
+    elif p > 0 and r.family == "f32":
+        masks = _masks_now(B, S, H, p, rng, sid, qkv.device)
     elif p > 0:
-        masks = alloc_masks(B, H, S, qkv.device)
+        masks = alloc_masks(B, H, S, qkv.device)   # the forward kernel call generates them
     else:
         masks = None
     sl = slopes.to(device=qkv.device, dtype=torch.float32).contiguous() if slopes is not None else None
-    # q/k/v are strided views into qkv: row stride 3*H*D, head stride D.
-    ld = 3 * H * D
-    base = qkv.data_ptr()
-    es = qkv.element_size()
-    args = (base, base + H * D * es, base + 2 * H * D * es, ctx.data_ptr(), lse.data_ptr(),
-            _lib.ptr(sl), _lib.ptr(masks), B, S, H, D, ld, H * D, int(causal), 1.0 / math.sqrt(D), float(p),
-            rng_ptr, sid)
-    if doc_range is not None:
-        doc = _doc_arg(doc_range, B, S, qkv.device)
-        _lib.call("dtd_attn_fwd_doc", *args, doc.data_ptr(), _lib.stream())
-    elif key_range is None:
-        _lib.call("dtd_attn_fwd", *args, _lib.stream())
+    args = (q, k, v, ctx.data_ptr(), lse.data_ptr(), _lib.ptr(sl), _lib.ptr(masks), B, S, H, D, ld, H * D, int(causal),
+            scale, float(p))
+    if r.family == "f32":
+        _lib.call(_ENTRY["f32"][0], *args, _lib.stream())
     else:
-        kr = _range_arg(key_range, B, qkv.device)
-        _lib.call("dtd_attn_fwd_range", *args, kr.data_ptr(), _lib.stream())
+        name, ranges, _keep = _range_ptrs(r, key_range, doc_range, B, S, qkv.device, False)
+        _lib.call(name, *args, rng_ptr, sid, *ranges, _lib.stream())
     return ctx, lse, masks
 
 
@@ -585,8 +636,9 @@ def attn_bwd(dctx, qkv, ctx, lse, B, S, H, D, causal=False, slopes=None, p=0.0, 
              doc_range: DocRange | torch.Tensor | None = None, kv_heads: int | None = None,
              window: int | None = None):
     """Returns dqkv [B*S, 3*H*D] in the qkv layout.  ``dbias`` = (dst, acc): also writes the
-    column sums of dqkv (the qkv projection's bias gradient) -- on the kernel path as per-wave
-    partials from the dQ / dK,dV epilogues (no extra pass over dqkv).
+    column sums of dqkv (the qkv projection's bias gradient) -- on the multi-head bf16 kernel path at
+    D = 64 as per-wave partials from the dQ / dK,dV epilogues (no extra pass over dqkv), everywhere
+    else in a pass of its own (``bias_grad``).
 
     ``key_range``: the forward's ranges.  Keys outside a range get zero dK / dV; the bf16 path
     runs the split dQ + dK/dV kernels (never a one-kernel form) and skips the key tiles / key
@@ -597,193 +649,41 @@ def attn_bwd(dctx, qkv, ctx, lse, B, S, H, D, causal=False, slopes=None, p=0.0, 
 
     ``kv_heads``: the forward's (grouped-query attention): dqkv is ``[B*S, (H + 2*Hkv)*D]``; one
     dK/dV workgroup per (key block, key/value head) sums its group's query heads in registers.
-    ``dbias`` then takes the column sums in a pass of its own (``bias_grad``).
 
     ``window``: the forward's sliding window: the split kernels of the windowed family, whose dK/dV
-    workgroups stop at the last query that sees one of their keys; ``dbias`` as with ``kv_heads``."""
+    workgroups stop at the last query that sees one of their keys."""
     from . import functional as Fx
-    _exclusive(key_range, doc_range)
-    Hkv = _kv_heads(kv_heads, H)
-    window = _window(window, S, causal, p, slopes)
-    if window:
-        dqkv = _attn_bwd_win(dctx, qkv, ctx, lse, B, S, H, Hkv, D, window, key_range, doc_range)
-        if dbias is not None:
-            Fx.bias_grad(dqkv, *dbias)
-        return dqkv
-    if Hkv != H:
-        dqkv = _attn_bwd_gqa(dctx, qkv, ctx, lse, B, S, H, Hkv, D, causal, slopes, p, key_range, doc_range)
-        if dbias is not None:
-            Fx.bias_grad(dqkv, *dbias)
-        return dqkv
-    if (key_range is not None or doc_range is not None) and qkv.dtype == torch.float32:
-        dqkv = attn_bwd_ref(dctx, qkv, ctx, lse, B, S, H, D, causal, slopes, p, rng, sid, key_range=key_range,
-                            doc_range=doc_range)
-        if dbias is not None:
-            Fx.bias_grad(dqkv, *dbias)
-        return dqkv
-    if f32_kernel_supported(qkv, D) and (p <= 0 or masks is not None):
-        dqkv = _attn_bwd_f32(dctx, qkv, ctx, lse, B, S, H, D, causal, slopes, p, masks)
-        if dbias is not None:
-            Fx.bias_grad(dqkv, *dbias)
-        return dqkv
-    if not kernel_supported(qkv, D):
-        dqkv = attn_bwd_ref(dctx, qkv, ctx, lse, B, S, H, D, causal, slopes, p, rng, sid, key_range=key_range,
-                            doc_range=doc_range)
-        if dbias is not None:
-            Fx.bias_grad(dqkv, *dbias)
-        return dqkv
-    dctx = dctx.contiguous()
-    dqkv = torch.empty_like(qkv)
-    delta = torch.empty((B, H, S), dtype=torch.float32, device=qkv.device)
-    sl = slopes.to(device=qkv.device, dtype=torch.float32).contiguous() if slopes is not None else None
-    ld = 3 * H * D
-    es = qkv.element_size()
-    qb, gb = qkv.data_ptr(), dqkv.data_ptr()
+    r = _route(qkv, B, S, H, D, causal, slopes, p, key_range, doc_range, kv_heads, window, True, masks)
     part = None
-    if dbias is not None and D == 64:
-        # one row per (batch, 32-row block of a 128-row workgroup tile); every entry is written
-        part = torch.empty((B * 4 * ((S + 127) // 128), ld), dtype=torch.float32, device=qkv.device)
-    args = (qb, qb + H * D * es, qb + 2 * H * D * es, ctx.data_ptr(), dctx.data_ptr(),
-            lse.data_ptr(), delta.data_ptr(), _lib.ptr(masks), gb, gb + H * D * es, gb + 2 * H * D * es,
-            _lib.ptr(sl), B, S, H, D, ld, H * D, int(causal), 1.0 / math.sqrt(D), float(p), _lib.ptr(part))
-    if doc_range is not None:
-        doc = _doc_arg(doc_range, B, S, qkv.device)
-        _lib.call("dtd_attn_bwd_doc", *args, doc.data_ptr(), _lib.stream())
-    elif key_range is None:
-        _lib.call("dtd_attn_bwd", *args, _lib.stream())
+    if r.family == "reference":
+        dqkv = attn_bwd_ref(dctx, qkv, ctx, lse, B, S, H, D, causal, slopes, p, rng, sid, key_range=key_range,
+                            doc_range=doc_range, kv_heads=r.Hkv, window=r.window)
     else:
-        kr = _range_arg(key_range, B, qkv.device)
-        _lib.call("dtd_attn_bwd_range", *args, kr.data_ptr(), _lib.stream())
-    if dbias is not None:
-        if part is not None:
-            dst, acc = dbias
-            Fx._finalize(part, part.shape[0], ld, (dst, acc), acc)
+        dctx = dctx.contiguous()
+        dqkv = torch.empty_like(qkv)
+        delta = torch.empty((B, H, S), dtype=torch.float32, device=qkv.device)
+        q, k, v, ld = _views(qkv, H, r.Hkv, D)
+        dq, dk, dv, _ = _views(dqkv, H, r.Hkv, D)
+        scale = 1.0 / math.sqrt(D)
+        head = (q, k, v, ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr(), delta.data_ptr())
+        if r.family == "f32":
+            name, ranges = _ENTRY["f32"][1], ()
         else:
-            Fx.bias_grad(dqkv, *dbias)
-    return dqkv
-
-
-def _gqa_ranges(key_range, doc_range, B, S, device):
-    """(key-range pointer, doc pointer, the tensors kept alive) of a grouped-query kernel call."""
-    kr = _range_arg(key_range, B, device) if key_range is not None else None
-    doc = _doc_arg(doc_range, B, S, device) if doc_range is not None else None
-    return _lib.ptr(kr), _lib.ptr(doc), (kr, doc)
-
-
-def _attn_fwd_gqa(qkv, B, S, H, Hkv, D, causal, slopes, p, key_range, doc_range):
-    _check_gqa(qkv, B, S, H, Hkv, D, p, slopes)
-    if not kernel_supported(qkv, D):
-        if qkv.is_cuda and qkv.dtype == torch.bfloat16 and D in (64, 128):
-            _gqa_entry("dtd_attn_fwd_gqa")     # a GPU without the kernels is an error, not a fallback
-        ctx, lse = attn_fwd_ref(qkv, B, S, H, D, causal, key_range=key_range, doc_range=doc_range, kv_heads=Hkv)
-        return ctx, lse, None
-    name = _gqa_entry("dtd_attn_fwd_gqa")
-    qkv = qkv.contiguous()
-    ctx = torch.empty((B * S, H * D), dtype=qkv.dtype, device=qkv.device)
-    lse = torch.empty((B, H, S), dtype=torch.float32, device=qkv.device)
-    ld, es, base = (H + 2 * Hkv) * D, qkv.element_size(), qkv.data_ptr()
-    krp, docp, _keep = _gqa_ranges(key_range, doc_range, B, S, qkv.device)
-    _lib.call(name, base, base + H * D * es, base + (H + Hkv) * D * es, ctx.data_ptr(), lse.data_ptr(), B, S, H, Hkv,
-              D, ld, H * D, int(causal), 1.0 / math.sqrt(D), krp, docp, _lib.stream())
-    return ctx, lse, None
-
-
-def _attn_bwd_gqa(dctx, qkv, ctx, lse, B, S, H, Hkv, D, causal, slopes, p, key_range, doc_range):
-    _check_gqa(qkv, B, S, H, Hkv, D, p, slopes)
-    if not kernel_supported(qkv, D):
-        if qkv.is_cuda and qkv.dtype == torch.bfloat16 and D in (64, 128):
-            _gqa_entry("dtd_attn_bwd_gqa")
-        return attn_bwd_ref(dctx, qkv, ctx, lse, B, S, H, D, causal, key_range=key_range, doc_range=doc_range,
-                            kv_heads=Hkv)
-    name = _gqa_entry("dtd_attn_bwd_gqa")
-    dctx = dctx.contiguous()
-    dqkv = torch.empty_like(qkv)
-    delta = torch.empty((B, H, S), dtype=torch.float32, device=qkv.device)
-    ld, es = (H + 2 * Hkv) * D, qkv.element_size()
-    qb, gb = qkv.data_ptr(), dqkv.data_ptr()
-    ko, vo = H * D * es, (H + Hkv) * D * es
-    krp, docp, _keep = _gqa_ranges(key_range, doc_range, B, S, qkv.device)
-    _lib.call(name, qb, qb + ko, qb + vo, ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr(), delta.data_ptr(),
-              gb, gb + ko, gb + vo, B, S, H, Hkv, D, ld, H * D, int(causal), 1.0 / math.sqrt(D), krp, docp,
-              _lib.stream())
-    return dqkv
-
-
-def _win_kernel(qkv, B, S, H, Hkv, D, name: str) -> bool:
-    """Whether a windowed call runs the kernels: bf16 on the GPU with D 64 / 128; fp32, CPU and other
-    head dims take the math reference.  A GPU build without the entry points is an error."""
-    if qkv.numel() != B * S * (H + 2 * Hkv) * D:
-        raise ValueError(f"qkv must be [B*S, (H + 2*Hkv)*D] = [{B * S}, {(H + 2 * Hkv) * D}], got {tuple(qkv.shape)}")
-    if not (qkv.is_cuda and qkv.dtype == torch.bfloat16 and D in (64, 128)):
-        return False
-    _win_entry(name)
-    return True
-
-
-def _attn_fwd_win(qkv, B, S, H, Hkv, D, window, key_range, doc_range):
-    name = "dtd_attn_fwd_win"
-    if not _win_kernel(qkv, B, S, H, Hkv, D, name):
-        ctx, lse = attn_fwd_ref(qkv, B, S, H, D, True, key_range=key_range, doc_range=doc_range, kv_heads=Hkv,
-                                window=window)
-        return ctx, lse, None
-    qkv = qkv.contiguous()
-    ctx = torch.empty((B * S, H * D), dtype=qkv.dtype, device=qkv.device)
-    lse = torch.empty((B, H, S), dtype=torch.float32, device=qkv.device)
-    # Hkv = H: [B, S, 3, H, D] is the q | k | v block layout with one query head per group
-    ld, es, base = (H + 2 * Hkv) * D, qkv.element_size(), qkv.data_ptr()
-    krp, docp, _keep = _gqa_ranges(key_range, doc_range, B, S, qkv.device)
-    _lib.call(name, base, base + H * D * es, base + (H + Hkv) * D * es, ctx.data_ptr(), lse.data_ptr(), B, S, H, Hkv,
-              D, ld, H * D, 1, 1.0 / math.sqrt(D), window, krp, docp, _lib.stream())
-    return ctx, lse, None
-
-
-def _attn_bwd_win(dctx, qkv, ctx, lse, B, S, H, Hkv, D, window, key_range, doc_range):
-    name = "dtd_attn_bwd_win"
-    if not _win_kernel(qkv, B, S, H, Hkv, D, name):
-        return attn_bwd_ref(dctx, qkv, ctx, lse, B, S, H, D, True, key_range=key_range, doc_range=doc_range,
-                            kv_heads=Hkv, window=window)
-    dctx = dctx.contiguous()
-    dqkv = torch.empty_like(qkv)
-    delta = torch.empty((B, H, S), dtype=torch.float32, device=qkv.device)
-    ld, es = (H + 2 * Hkv) * D, qkv.element_size()
-    qb, gb = qkv.data_ptr(), dqkv.data_ptr()
-    ko, vo = H * D * es, (H + Hkv) * D * es
-    krp, docp, _keep = _gqa_ranges(key_range, doc_range, B, S, qkv.device)
-    _lib.call(name, qb, qb + ko, qb + vo, ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr(), delta.data_ptr(),
-              gb, gb + ko, gb + vo, B, S, H, Hkv, D, ld, H * D, 1, 1.0 / math.sqrt(D), window, krp, docp,
-              _lib.stream())
-    return dqkv
-
-
-def _attn_fwd_f32(qkv, B, S, H, D, causal, slopes, p, rng, sid, masks):
-    qkv = qkv.contiguous()
-    ctx = torch.empty((B * S, H * D), dtype=qkv.dtype, device=qkv.device)
-    lse = torch.empty((B, H, S), dtype=torch.float32, device=qkv.device)
-    if p > 0:
-        if masks is not None:
-            torch.cuda.current_stream(qkv.device).wait_event(masks.event)
-            masks = masks.masks
+            name, ranges, _keep = _range_ptrs(r, key_range, doc_range, B, S, qkv.device, True)
+        if r.family in ("gqa", "win"):
+            win = (1, scale, r.window) if r.window else (int(causal), scale)
+            _lib.call(name, *head, dq, dk, dv, B, S, H, r.Hkv, D, ld, H * D, *win, *ranges, _lib.stream())
         else:
-            masks = _masks_now(B, S, H, p, rng, sid, qkv.device)
-    else:
-        masks = None
-    sl = slopes.to(device=qkv.device, dtype=torch.float32).contiguous() if slopes is not None else None
-    ld, es, base = 3 * H * D, qkv.element_size(), qkv.data_ptr()
-    _lib.call("dtd_attn_fwd_f32", base, base + H * D * es, base + 2 * H * D * es, ctx.data_ptr(), lse.data_ptr(),
-              _lib.ptr(sl), _lib.ptr(masks), B, S, H, D, ld, H * D, int(causal), 1.0 / math.sqrt(D), float(p),
-              _lib.stream())
-    return ctx, lse, masks
-
-
-def _attn_bwd_f32(dctx, qkv, ctx, lse, B, S, H, D, causal, slopes, p, masks):
-    dctx = dctx.contiguous()
-    dqkv = torch.empty_like(qkv)
-    delta = torch.empty((B, H, S), dtype=torch.float32, device=qkv.device)
-    sl = slopes.to(device=qkv.device, dtype=torch.float32).contiguous() if slopes is not None else None
-    ld, es = 3 * H * D, qkv.element_size()
-    qb, gb = qkv.data_ptr(), dqkv.data_ptr()
-    _lib.call("dtd_attn_bwd_f32", qb, qb + H * D * es, qb + 2 * H * D * es, ctx.data_ptr(), dctx.data_ptr(),
-              lse.data_ptr(), delta.data_ptr(), _lib.ptr(masks if p > 0 else None), gb, gb + H * D * es,
-              gb + 2 * H * D * es, _lib.ptr(sl), B, S, H, D, ld, H * D, int(causal), 1.0 / math.sqrt(D), float(p),
-              _lib.stream())
+            sl = slopes.to(device=qkv.device, dtype=torch.float32).contiguous() if slopes is not None else None
+            if r.family == "mha" and dbias is not None and D == 64:
+                # one row per (batch, 32-row block of a 128-row workgroup tile); every entry is written
+                part = torch.empty((B * 4 * ((S + 127) // 128), ld), dtype=torch.float32, device=qkv.device)
+            tail = (_lib.ptr(part),) if r.family == "mha" else ()
+            _lib.call(name, *head, _lib.ptr(masks if p > 0 else None), dq, dk, dv, _lib.ptr(sl), B, S, H, D, ld, H * D,
+                      int(causal), scale, float(p), *tail, *ranges, _lib.stream())
+    if dbias is not None and part is not None:
+        dst, acc = dbias
+        Fx._finalize(part, part.shape[0], ld, (dst, acc), acc)
+    elif dbias is not None:
+        Fx.bias_grad(dqkv, *dbias)
     return dqkv

@@ -194,13 +194,18 @@ struct FwdArgs {
   int B, S, H, ld, ldo, causal, W;
   float scale, p, thr;
   const int* kv_range;    // optional [B][2] = (lo, hi): key j of sequence b takes part iff lo <= j < hi (RANGE kernels)
-  // DOC kernels (sequence packing) read another array through the same field, so that the argument
-  // block -- and with it the other instantiations' register figures -- stays as it was: [B][S][2] =
-  // half-open span (lo, hi) of each position's document ((0, 0) for a pad), followed at once by
-  // [B][ceil(S/128)][2] = (min lo, max hi) over each 128-position block's non-empty rows ((0, 0) for
-  // a block without one).  // GQA kernels (no dropout, so no keep words) likewise read Hkv, the number of key/value heads,
-  // from W -- here and in BwdArgs.  The sliding-window kernels (grouped-query forms, so no dropout
-  // either) read the window, an integer, from the bits of p -- here and in BwdArgs.
+  // Three fields carry a second meaning in the kernel families that cannot use the first, so that the
+  // argument block -- and with it the other instantiations' register figures -- stays as it was.  Only
+  // fwd_args / bwd_args (host) write them that way, and the kernels read them through these accessors:
+  //  * hkv(): the number of key/value heads, in W (GQA and window kernels: no dropout, so no keep words);
+  //  * window(): the sliding window, an integer, in the bits of p (window kernels: no dropout either);
+  //  * doc(): in kv_range (DOC kernels), [B][S][2] = half-open span (lo, hi) of each position's document
+  //    ((0, 0) for a pad), followed at once by [B][ceil(S/128)][2] = (min lo, max hi) over each
+  //    128-position block's non-empty rows ((0, 0) for a block without one).
+  // The same holds for BwdArgs.
+  __device__ __forceinline__ int hkv() const { return W; }
+  __device__ __forceinline__ int window() const { return __float_as_int(p); }
+  __device__ __forceinline__ const int* doc() const { return kv_range; }
 };
 
 // Key range of sequence b, clamped to [0, S]; b is workgroup-uniform, so both are scalar loads and
@@ -519,7 +524,7 @@ struct TileLoader {
 // and only the key tiles floor(lo / BN) .. ceil(min(hi, causal end) / BN) - 1 are visited.  A row
 // left without a key (lo >= hi, or causal with q < lo) ends with m = -inf, l = 0: ctx 0, lse -inf.
 // DOC (sequence packing, instead of RANGE): every lane holds the document span of its query (the
-// spans a.kv_range then points to): key j takes part iff it lies inside it.  The tile range comes
+// spans of a.doc()): key j takes part iff it lies inside it.  The tile range comes
 // from the 128-query block's bounds (the array behind the spans) exactly as RANGE's comes from the
 // sequence's; a tile is masked when some lane's span does not cover it (a wave-uniform vote).  A
 // block without a non-empty row runs no tile and writes the empty rows.  The DOC form is a kernel of its own name, attn_fwd_doc_kernel,
@@ -536,7 +541,7 @@ __global__ void __launch_bounds__(256, OCC) attn_fwd_doc_kernel(FwdArgs a) {
 }
 // Grouped-query form (Hkv < H key/value heads, query head h reads key/value head h / (H / Hkv)): a
 // kernel of its own name again.  MODE 0: plain, 1: key range, 2: document spans.  No dropout, no
-// ALiBi; the argument block is FwdArgs as it stands, with Hkv in the (then unused) field W.
+// ALiBi; the argument block is FwdArgs as it stands, with Hkv as a.hkv().
 template <int D, int OCC, int BN, int RING, int MODE>
 __global__ void __launch_bounds__(256, OCC) attn_fwd_gqa_kernel(FwdArgs a) {
   constexpr bool PK = false, RANGE = MODE == 1, DOC = MODE == 2, GQA = true, WIN = false;
@@ -544,7 +549,7 @@ __global__ void __launch_bounds__(256, OCC) attn_fwd_gqa_kernel(FwdArgs a) {
 }
 // Sliding-window form of the grouped-query kernel (dtd_attn_fwd_win; causal only): query i sees key j
 // iff i - win < j <= i, intersected with MODE's key range / document span.  A kernel of its own name
-// once more.  The window is an integer carried in FwdArgs::p (no dropout here), Hkv in W as above;
+// once more.  The window is a.window() (FwdArgs; no dropout here), Hkv a.hkv() as above;
 // Hkv = H (G = 1) is the multi-head layout.  The key tiles start at floor(max(lo, qblk - win + 1) / BN);
 // a tile whose first key the wave's last query no longer sees takes the masked path.  The waves of a
 // block start seeing keys at different tiles, so a wave can meet leading tiles it masks whole while
@@ -745,8 +750,11 @@ struct BwdArgs {
   // optional [B * 4 * ceil(S/128)][3 H D] fp32 column partials of dqkv (the qkv bias gradient):
   // one row per (batch, 32-row block of a wave), finished by colsum_finalize
   float* bias_part;
-  const int* kv_range;    // optional [B][2] key range per sequence (see FwdArgs; RANGE kernels only)
-                          // (DOC kernels: the document spans and block bounds, see FwdArgs)
+  const int* kv_range;    // optional [B][2] key range per sequence (RANGE kernels)
+  // the second meanings of W, p and kv_range: see FwdArgs
+  __device__ __forceinline__ int hkv() const { return W; }
+  __device__ __forceinline__ int window() const { return __float_as_int(p); }
+  __device__ __forceinline__ const int* doc() const { return kv_range; }
 };
 
 // Column sums of a wave's 32 rows x 64 columns of dQ / dK / dV, straight from the accumulators
@@ -1461,8 +1469,39 @@ static int bwd_form() {
 static bool bwd_fused() { return bwd_form() != 0; }
 static bool bwd_fused8() { return bwd_form() == 1; }
 
-// q,k,v,o: bf16 views with row stride ld (q/k/v) / ldo (o); lse: [B,H,S] fp32.
-// masks: [2][B*H*S*W] uint32 (W = ceil(S/32)) written here when p > 0 (read by the backward).
+// ---- Host side: one launch path for every kernel family -------------------------------------------
+// Every exported dtd_attn_fwd* / dtd_attn_bwd* entry point is a shim over attn_fwd_launch /
+// attn_bwd_launch, which check the call (check_call), fill the argument block (fwd_args / bwd_args)
+// and pick the kernels: the family's and MODE's instantiation in the tile forms of TileForm, or, for
+// the plain multi-head call alone, the environment-selected forms (launch_fwd_plain / launch_bwd_plain).
+
+// kMha: H key/value heads; dropout and ALiBi.  kGqa: Hkv < H key/value heads (H % Hkv == 0), k / v hold
+// Hkv heads of D columns; no dropout, no ALiBi.  kWin: kGqa with a causal window of `window` keys per
+// query and 1 <= Hkv <= H (with Hkv = H the q | k | v blocks of a multi-head qkv are this layout with
+// one query head per group).
+enum Family { kMha = 0, kGqa = 1, kWin = 2 };
+
+// kv_range: nullptr, or device int32 [B][2] = (lo, hi) key range per sequence (key-padding mask).
+// doc: nullptr, or the device int32 [B][S][2] document spans followed by the [B][ceil(S/128)][2] block
+// bounds of a packed batch (FwdArgs::doc).  At most one of them.  The kernels' MODE:
+static int mode_of(const int* kv_range, const int* doc) { return doc ? 2 : kv_range ? 1 : 0; }
+
+// f(std::integral_constant<int, v>{}) for a runtime v in [0, N): the compile-time constants of a launch.
+// (Kernels are emitted in the order in which the host code first names their instantiations: N - 1
+// first here, families in the order of `Family`, D = 64 before 128 -- the order they have always had.)
+template <int N, class F>
+static void with_const(int v, F&& f) {
+  if (v >= N - 1) return f(std::integral_constant<int, N - 1>{});
+  if constexpr (N > 1) with_const<N - 1>(v, f);
+}
+// ... and for a runtime Family
+template <class F>
+static void with_family(Family fam, F&& f) {
+  if (fam == kMha) f(std::integral_constant<int, kMha>{});
+  else if (fam == kGqa) f(std::integral_constant<int, kGqa>{});
+  else f(std::integral_constant<int, kWin>{});
+}
+
 // The tile loads address one (batch, head)'s rows through 32-bit buffer offsets (RowSrc).
 static bool offsets_fit(int S, int ld, int ldo) {
   const long long lim = 0x7fffffffLL;
@@ -1470,66 +1509,124 @@ static bool offsets_fit(int S, int ld, int ldo) {
   return (long long)S * ld * 2 < lim && (long long)S * ldo * 2 < lim && 32 * W * W * 4 < lim;
 }
 
-// kv_range: nullptr, or device int32 [B][2] = (lo, hi) key range per sequence (key-padding mask);
-// the ranged call always takes attn_fwd_kernel's RANGE form (no pipe / packed-fp32 variants).
-// doc: nullptr, or the device int32 [B][S][2] document spans followed by the [B][ceil(S/128)][2]
-// block bounds of a packed batch (FwdArgs): attn_fwd_doc_kernel.
-static int attn_fwd_launch(const void* q, const void* k, const void* v, void* o, float* lse, const float* slopes,
-                           uint32_t* masks, int B, int S, int H, int D, int ld, int ldo, int causal, float scale,
-                           float p, const uint64_t* rng, uint32_t sid, const int* kv_range, const int* doc,
-                           hipStream_t s) {
-  if (B * S * H == 0) return 0;
+// What every entry point requires of a call.  0: launch; -1: nothing to do (an empty call, whatever
+// else it holds); otherwise the error to return.
+static int check_call(Family fam, int B, int S, int H, int Hkv, int D, int ld, int ldo, int causal, int window,
+                      const int* kv_range, const int* doc) {
+  if (B * S * H == 0) return -1;
+  if (fam == kWin && (window <= 0 || !causal)) return (int)hipErrorInvalidValue;
+  if (fam != kMha && (Hkv <= 0 || Hkv > H || H % Hkv || (fam == kGqa && Hkv == H))) return (int)hipErrorInvalidValue;
   if (kv_range && doc) return (int)hipErrorInvalidValue;
+  if (D != 64 && D != 128) return (int)hipErrorInvalidValue;
   if (!offsets_fit(S, ld, ldo)) return (int)hipErrorInvalidValue;
+  return 0;
+}
+
+static float rescale_thr() {
+  const char* e = getenv("DTD_ATTN_RESCALE_THR");
+  return e ? (float)atof(e) : kRescaleThr;
+}
+
+static float window_bits(int window) {
+  float f;
+  memcpy(&f, &window, sizeof f);
+  return f;
+}
+
+// The argument blocks.  masks: the keep bits [2][B*H*S*W] (W = ceil(S/32)) or nullptr (no dropout).
+// hkv (0: the multi-head family) and window (0: none) go where FwdArgs says: the only host code that
+// writes W, p and kv_range with their second meanings.
+static FwdArgs fwd_args(const void* q, const void* k, const void* v, void* o, float* lse, const float* slopes,
+                        const uint32_t* masks, int B, int S, int H, int ld, int ldo, int causal, float scale, float p,
+                        int hkv, int window, const int* kv_range, const int* doc) {
   const int W = (S + 31) / 32;
-  uint32_t* mA = nullptr;
-  if (p > 0.f) {
-    if (!masks) return (int)hipErrorInvalidValue;
-    mA = masks;
-    // rng == nullptr: the masks were generated ahead of time by dtd_attn_masks (on a side
-    // stream, overlapping the QKV GEMM)
-    if (rng) {
-      uint32_t* mB = masks + (size_t)B * H * (32 * W) * W;
-      hipLaunchKernelGGL(attn_mask_kernel, dim3((S + 255) / 256, B * H), dim3(256), 0, s, mA, mB, S, W, rng, sid,
-                         keep_threshold(p));
-    }
-  }
-  const char* thr_env = getenv("DTD_ATTN_RESCALE_THR");
-  const float thr = thr_env ? (float)atof(thr_env) : kRescaleThr;
-  const uint32_t* mBk = mA ? mA + (size_t)B * H * (32 * W) * W : nullptr;
-  FwdArgs a{(const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, lse, slopes, mA, mBk, B, S, H, ld, ldo, causal, W,
-            scale, p, thr, doc ? doc : kv_range};
-  dim3 grid((S + 127) / 128, B * H);
-  if (doc) {
-    if (D == 64) hipLaunchKernelGGL((attn_fwd_doc_kernel<64, 3, 64, 1>), grid, dim3(256), 0, s, a);
-    else if (D == 128) hipLaunchKernelGGL((attn_fwd_doc_kernel<128, 1, 64, 2>), grid, dim3(256), 0, s, a);
-    else return (int)hipErrorInvalidValue;
-  } else if (kv_range) {
-    if (D == 64) hipLaunchKernelGGL((attn_fwd_kernel<64, 3, 64, 1, false, true>), grid, dim3(256), 0, s, a);
-    else if (D == 128) hipLaunchKernelGGL((attn_fwd_kernel<128, 1, 64, 2, false, true>), grid, dim3(256), 0, s, a);
-    else return (int)hipErrorInvalidValue;
-  } else if (D == 64 && fwd_pipe()) {
+  FwdArgs a{(const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, lse, slopes, masks,
+            masks ? masks + (size_t)B * H * (32 * W) * W : nullptr, B, S, H, ld, ldo, causal, hkv ? hkv : W,
+            scale, p, rescale_thr(), doc ? doc : kv_range};
+  if (window) a.causal = 1, a.p = window_bits(window < S ? window : S);
+  return a;
+}
+static BwdArgs bwd_args(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                        float* delta, const uint32_t* masks, void* dq, void* dk, void* dv, const float* slopes, int B,
+                        int S, int H, int ld, int ldo, int causal, float scale, float p, float* bias_part, int hkv,
+                        int window, const int* kv_range, const int* doc) {
+  const int W = (S + 31) / 32;
+  BwdArgs a{(const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)dout, lse, delta, (const bf16*)o,
+            (bf16*)dq, (bf16*)dk, (bf16*)dv, slopes, masks, masks ? masks + (size_t)B * H * (32 * W) * W : nullptr,
+            B, S, H, ld, ldo, causal, hkv ? hkv : W, scale, p, bias_part, doc ? doc : kv_range};
+  if (window) a.causal = 1, a.p = window_bits(window < S ? window : S);
+  return a;
+}
+
+// The tile forms of every call but the plain multi-head one (the default forms of the kernels they
+// derive from): <D, OCC, BN, RING> of the forward and dQ, <D, KV_OCC, KV_BM> of dK/dV.
+template <int D> struct TileForm;
+template <> struct TileForm<64> { static constexpr int OCC = 3, BN = 64, RING = 1, KV_OCC = 2, KV_BM = 128; };
+template <> struct TileForm<128> { static constexpr int OCC = 1, BN = 64, RING = 2, KV_OCC = 1, KV_BM = 64; };
+
+// Dropout keep-bit masks of one attention call ([2][B*H*S*W] uint32), VALU-only
+static void launch_masks(uint32_t* masks, int B, int S, int H, float p, const uint64_t* rng, uint32_t sid, hipStream_t s) {
+  const int W = (S + 31) / 32;
+  hipLaunchKernelGGL(attn_mask_kernel, dim3((S + 255) / 256, B * H), dim3(256), 0, s, masks,
+                     masks + (size_t)B * H * (32 * W) * W, S, W, rng, sid, keep_threshold(p));
+}
+
+// The plain multi-head forward: the forms the environment selects (fwd_pipe, occupancy, fwd_pk)
+template <int D>
+static void launch_fwd_plain(dim3 grid, hipStream_t s, const FwdArgs& a) {
+  if constexpr (D == 128) {
+    hipLaunchKernelGGL((attn_fwd_kernel<128, 1, 64, 2>), grid, dim3(256), 0, s, a);
+  } else if (fwd_pipe()) {
     // two score tiles live: 198 VGPRs, 2 waves / SIMD (at 3 it spills)
     hipLaunchKernelGGL((attn_fwd_pipe_kernel<64, 2, 64>), grid, dim3(256), 0, s, a);
-  } else if (D == 64) {
+  } else {
     const int o = occupancy(0);
     if (o >= 3 && fwd_pk()) hipLaunchKernelGGL((attn_fwd_kernel<64, 3, 64, 1, true>), grid, dim3(256), 0, s, a);
     else if (o >= 3) hipLaunchKernelGGL((attn_fwd_kernel<64, 3, 64, 1>), grid, dim3(256), 0, s, a);
     else if (o == 2) hipLaunchKernelGGL((attn_fwd_kernel<64, 2, 64, 2>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((attn_fwd_kernel<64, 1, 64, 2>), grid, dim3(256), 0, s, a);
-  } else if (D == 128) {
-    hipLaunchKernelGGL((attn_fwd_kernel<128, 1, 64, 2>), grid, dim3(256), 0, s, a);
-  } else {
-    return (int)hipErrorInvalidValue;
   }
+}
+
+// Every other forward: the ranged multi-head call takes attn_fwd_kernel's RANGE form (no pipe /
+// packed-fp32 variants), the packed one attn_fwd_doc_kernel.
+template <int D, int FAM, int MODE>
+static void launch_fwd_form(dim3 grid, hipStream_t s, const FwdArgs& a) {
+  using T = TileForm<D>;
+  if constexpr (FAM == kWin) hipLaunchKernelGGL((attn_fwd_win_kernel<D, T::OCC, T::BN, T::RING, MODE>), grid, dim3(256), 0, s, a);
+  else if constexpr (FAM == kGqa) hipLaunchKernelGGL((attn_fwd_gqa_kernel<D, T::OCC, T::BN, T::RING, MODE>), grid, dim3(256), 0, s, a);
+  else if constexpr (MODE == 2) hipLaunchKernelGGL((attn_fwd_doc_kernel<D, T::OCC, T::BN, T::RING>), grid, dim3(256), 0, s, a);
+  else if constexpr (MODE == 1) hipLaunchKernelGGL((attn_fwd_kernel<D, T::OCC, T::BN, T::RING, false, true>), grid, dim3(256), 0, s, a);
+  else launch_fwd_plain<D>(grid, s, a);
+}
+
+// q,k,v,o: bf16 views with row stride ld (q/k/v) / ldo (o); lse: [B,H,S] fp32.
+// masks: [2][B*H*S*W] uint32 (W = ceil(S/32)), written here when p > 0 and rng is given (read by the
+// backward); rng == nullptr: they were generated ahead of time by dtd_attn_masks (on a side stream,
+// overlapping the QKV GEMM).
+static int attn_fwd_launch(Family fam, const void* q, const void* k, const void* v, void* o, float* lse,
+                           const float* slopes, uint32_t* masks, int B, int S, int H, int Hkv, int D, int ld, int ldo,
+                           int causal, float scale, float p, const uint64_t* rng, uint32_t sid, int window,
+                           const int* kv_range, const int* doc, hipStream_t s) {
+  if (const int rc = check_call(fam, B, S, H, Hkv, D, ld, ldo, causal, window, kv_range, doc)) return rc < 0 ? 0 : rc;
+  if (p > 0.f && !masks) return (int)hipErrorInvalidValue;
+  if (p > 0.f && rng) launch_masks(masks, B, S, H, p, rng, sid, s);
+  const FwdArgs a = fwd_args(q, k, v, o, lse, slopes, p > 0.f ? masks : nullptr, B, S, H, ld, ldo, causal, scale, p,
+                             fam == kMha ? 0 : Hkv, window, kv_range, doc);
+  const dim3 grid((S + 127) / 128, B * H);
+  with_family(fam, [&](auto f) { with_const<3>(mode_of(kv_range, doc), [&](auto m) {
+    constexpr int FAM = decltype(f)::value, MODE = decltype(m)::value;
+    if (D == 64) launch_fwd_form<64, FAM, MODE>(grid, s, a);
+    else launch_fwd_form<128, FAM, MODE>(grid, s, a);
+  }); });
   DTD_LAUNCH_CHECK();
 }
 
 DTD_EXPORT int dtd_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const float* slopes,
                             uint32_t* masks, int B, int S, int H, int D, int ld, int ldo, int causal, float scale,
                             float p, const uint64_t* rng, uint32_t sid, hipStream_t s) {
-  return attn_fwd_launch(q, k, v, o, lse, slopes, masks, B, S, H, D, ld, ldo, causal, scale, p, rng, sid, nullptr,
-                         nullptr, s);
+  return attn_fwd_launch(kMha, q, k, v, o, lse, slopes, masks, B, S, H, H, D, ld, ldo, causal, scale, p, rng, sid, 0,
+                         nullptr, nullptr, s);
 }
 
 // dtd_attn_fwd with a per-sequence key range (kv_range: device int32 [B][2], required)
@@ -1538,8 +1635,8 @@ DTD_EXPORT int dtd_attn_fwd_range(const void* q, const void* k, const void* v, v
                                   int causal, float scale, float p, const uint64_t* rng, uint32_t sid,
                                   const int* kv_range, hipStream_t s) {
   if (!kv_range) return (int)hipErrorInvalidValue;
-  return attn_fwd_launch(q, k, v, o, lse, slopes, masks, B, S, H, D, ld, ldo, causal, scale, p, rng, sid, kv_range,
-                         nullptr, s);
+  return attn_fwd_launch(kMha, q, k, v, o, lse, slopes, masks, B, S, H, H, D, ld, ldo, causal, scale, p, rng, sid, 0,
+                         kv_range, nullptr, s);
 }
 
 // dtd_attn_fwd for a packed batch: doc = device int32 [B][S][2] document span of every position,
@@ -1548,68 +1645,24 @@ DTD_EXPORT int dtd_attn_fwd_doc(const void* q, const void* k, const void* v, voi
                                 uint32_t* masks, int B, int S, int H, int D, int ld, int ldo, int causal, float scale,
                                 float p, const uint64_t* rng, uint32_t sid, const int* doc, hipStream_t s) {
   if (!doc) return (int)hipErrorInvalidValue;
-  return attn_fwd_launch(q, k, v, o, lse, slopes, masks, B, S, H, D, ld, ldo, causal, scale, p, rng, sid, nullptr,
-                         doc, s);
+  return attn_fwd_launch(kMha, q, k, v, o, lse, slopes, masks, B, S, H, H, D, ld, ldo, causal, scale, p, rng, sid, 0,
+                         nullptr, doc, s);
 }
 
-// Grouped-query forward: Hkv < H key/value heads (H % Hkv == 0), k / v hold Hkv heads of D columns.
-// No dropout, no ALiBi.  kv_range / doc: at most one, as in attn_fwd_launch; the kernels take the
-// default tile forms of the multi-head kernels they derive from.
-template <int MODE>
-static void launch_fwd_gqa(int D, dim3 grid, hipStream_t s, const FwdArgs& a) {
-  if (D == 64) hipLaunchKernelGGL((attn_fwd_gqa_kernel<64, 3, 64, 1, MODE>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((attn_fwd_gqa_kernel<128, 1, 64, 2, MODE>), grid, dim3(256), 0, s, a);
-}
+// Grouped-query forward (Family kGqa).  kv_range / doc: at most one, either may be null.
 DTD_EXPORT int dtd_attn_fwd_gqa(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H,
                                 int Hkv, int D, int ld, int ldo, int causal, float scale, const int* kv_range,
                                 const int* doc, hipStream_t s) {
-  if (B * S * H == 0) return 0;
-  if (Hkv <= 0 || Hkv >= H || H % Hkv) return (int)hipErrorInvalidValue;
-  if (kv_range && doc) return (int)hipErrorInvalidValue;
-  if (D != 64 && D != 128) return (int)hipErrorInvalidValue;
-  if (!offsets_fit(S, ld, ldo)) return (int)hipErrorInvalidValue;
-  const char* thr_env = getenv("DTD_ATTN_RESCALE_THR");
-  const float thr = thr_env ? (float)atof(thr_env) : kRescaleThr;
-  FwdArgs a{(const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, lse, nullptr, nullptr, nullptr, B, S, H, ld, ldo,
-            causal, /*W = */ Hkv, scale, 0.f, thr, doc ? doc : kv_range};
-  dim3 grid((S + 127) / 128, B * H);
-  if (doc) launch_fwd_gqa<2>(D, grid, s, a);
-  else if (kv_range) launch_fwd_gqa<1>(D, grid, s, a);
-  else launch_fwd_gqa<0>(D, grid, s, a);
-  DTD_LAUNCH_CHECK();
+  return attn_fwd_launch(kGqa, q, k, v, o, lse, nullptr, nullptr, B, S, H, Hkv, D, ld, ldo, causal, scale, 0.f, nullptr,
+                         0, 0, kv_range, doc, s);
 }
 
-// Sliding-window forward (attn_fwd_win_kernel): dtd_attn_fwd_gqa with a causal window of `window`
-// keys per query.  1 <= Hkv <= H: with Hkv = H the q | k | v blocks of a multi-head qkv are this
-// layout with one query head per group.  The window travels in the argument block's p.
-template <int MODE>
-static void launch_fwd_win(int D, dim3 grid, hipStream_t s, const FwdArgs& a) {
-  if (D == 64) hipLaunchKernelGGL((attn_fwd_win_kernel<64, 3, 64, 1, MODE>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((attn_fwd_win_kernel<128, 1, 64, 2, MODE>), grid, dim3(256), 0, s, a);
-}
-static float window_bits(int window) {
-  float f;
-  memcpy(&f, &window, sizeof f);
-  return f;
-}
+// Sliding-window forward (Family kWin): dtd_attn_fwd_gqa with a causal window of `window` keys per query
 DTD_EXPORT int dtd_attn_fwd_win(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H,
                                 int Hkv, int D, int ld, int ldo, int causal, float scale, int window,
                                 const int* kv_range, const int* doc, hipStream_t s) {
-  if (window <= 0 || !causal) return (int)hipErrorInvalidValue;
-  if (Hkv <= 0 || Hkv > H || H % Hkv) return (int)hipErrorInvalidValue;
-  if (kv_range && doc) return (int)hipErrorInvalidValue;
-  if (D != 64 && D != 128) return (int)hipErrorInvalidValue;
-  if (B * S * H == 0) return 0;
-  if (!offsets_fit(S, ld, ldo)) return (int)hipErrorInvalidValue;
-  const char* thr_env = getenv("DTD_ATTN_RESCALE_THR");
-  const float thr = thr_env ? (float)atof(thr_env) : kRescaleThr;
-  FwdArgs a{(const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, lse, nullptr, nullptr, nullptr, B, S, H, ld, ldo,
-            1, /*W = */ Hkv, scale, /*p = */ window_bits(window < S ? window : S), thr, doc ? doc : kv_range};
-  dim3 grid((S + 127) / 128, B * H);
-  if (doc) launch_fwd_win<2>(D, grid, s, a);
-  else if (kv_range) launch_fwd_win<1>(D, grid, s, a);
-  else launch_fwd_win<0>(D, grid, s, a);
-  DTD_LAUNCH_CHECK();
+  return attn_fwd_launch(kWin, q, k, v, o, lse, nullptr, nullptr, B, S, H, Hkv, D, ld, ldo, causal, scale, 0.f, nullptr,
+                         0, window, kv_range, doc, s);
 }
 
 // 0 = the dQ + dK/dV pair, 1 = fused where it applies, 2 = fused, 4-wave form; returns the previous
@@ -1621,15 +1674,13 @@ DTD_EXPORT int dtd_attn_set_bwd_form(int f) {
   return old;
 }
 
-// Dropout keep-bit masks of one attention call ([2][B*H*S*W] uint32), VALU-only: launched on a
-// side stream so it runs concurrently with the (MFMA-bound) QKV projection GEMM.
+// The keep bits of a call generated ahead of it: launched on a side stream so that the generator runs
+// concurrently with the (MFMA-bound) QKV projection GEMM.
 DTD_EXPORT int dtd_attn_masks(uint32_t* masks, int B, int S, int H, float p, const uint64_t* rng, uint32_t sid,
                               hipStream_t s) {
   if (B * S * H == 0 || p <= 0.f) return 0;
   if (!masks || !rng) return (int)hipErrorInvalidValue;
-  const int W = (S + 31) / 32;
-  hipLaunchKernelGGL(attn_mask_kernel, dim3((S + 255) / 256, B * H), dim3(256), 0, s, masks,
-                     masks + (size_t)B * H * (32 * W) * W, S, W, rng, sid, keep_threshold(p));
+  launch_masks(masks, B, S, H, p, rng, sid, s);
   DTD_LAUNCH_CHECK();
 }
 
@@ -1647,25 +1698,16 @@ static void launch_dkdv(dim3 grid, hipStream_t s, const BwdArgs& a) {
   else hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, OCC, BM, false, false>), grid, dim3(256), 0, s, a);
 }
 
-// With a key range: always the masked form -- the blocks holding lo / hi need it even where
-// launch_dkdv would pick MASK = false.
-template <int D, int OCC, int BM>
-static void launch_dkdv_range(dim3 grid, hipStream_t s, const BwdArgs& a) {
-  const bool drop = a.maskB != nullptr, alibi = a.slopes != nullptr;
-  if (drop && alibi) hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, OCC, BM, true, true, true, true>), grid, dim3(256), 0, s, a);
-  else if (drop) hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, OCC, BM, true, false, true, true>), grid, dim3(256), 0, s, a);
-  else if (alibi) hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, OCC, BM, false, true, true, true>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, OCC, BM, false, false, true, true>), grid, dim3(256), 0, s, a);
-}
-
-// With document spans: attn_bwd_dkdv_doc_kernel, the masked form as well.
-template <int D, int OCC, int BM>
-static void launch_dkdv_doc(dim3 grid, hipStream_t s, const BwdArgs& a) {
-  const bool drop = a.maskB != nullptr, alibi = a.slopes != nullptr;
-  if (drop && alibi) hipLaunchKernelGGL((attn_bwd_dkdv_doc_kernel<D, OCC, BM, true, true>), grid, dim3(256), 0, s, a);
-  else if (drop) hipLaunchKernelGGL((attn_bwd_dkdv_doc_kernel<D, OCC, BM, true, false>), grid, dim3(256), 0, s, a);
-  else if (alibi) hipLaunchKernelGGL((attn_bwd_dkdv_doc_kernel<D, OCC, BM, false, true>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((attn_bwd_dkdv_doc_kernel<D, OCC, BM, false, false>), grid, dim3(256), 0, s, a);
+// Multi-head dK/dV with a key range (MODE 1) or document spans (MODE 2, attn_bwd_dkdv_doc_kernel):
+// always the masked form -- the blocks holding lo / hi need it even where launch_dkdv would pick
+// MASK = false.
+template <int D, int OCC, int BM, int MODE>
+static void launch_dkdv_masked(dim3 grid, hipStream_t s, const BwdArgs& a) {
+  with_const<2>(a.maskB != nullptr, [&](auto drop) { with_const<2>(a.slopes != nullptr, [&](auto alibi) {
+    constexpr bool DROP = decltype(drop)::value, ALIBI = decltype(alibi)::value;
+    if constexpr (MODE == 2) hipLaunchKernelGGL((attn_bwd_dkdv_doc_kernel<D, OCC, BM, DROP, ALIBI>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, OCC, BM, DROP, ALIBI, true, true>), grid, dim3(256), 0, s, a);
+  }); });
 }
 
 // Which kernels of the split backward run (bit 0: dQ, bit 1: dK/dV): a timing hook for
@@ -1678,58 +1720,22 @@ DTD_EXPORT int dtd_attn_set_bwd_kernels(int mask) {
   return old;
 }
 
-// dq/dk/dv: bf16 views with row stride ld into dqkv.  `delta` is [B,H,S] fp32 scratch.
-// kv_range: nullptr, or device int32 [B][2] key range per sequence; the ranged call always runs
-// the split dQ + dK/dV pair in its default tile forms.  doc (see attn_fwd_launch): likewise.
-static int attn_bwd_launch(const void* q, const void* k, const void* v, const void* o, const void* dout,
-                           const float* lse, float* delta, const uint32_t* masks, void* dq, void* dk, void* dv,
-                           const float* slopes, int B, int S, int H, int D, int ld, int ldo, int causal, float scale,
-                           float p, float* bias_part, const int* kv_range, const int* doc, hipStream_t s) {
-  if (B * S * H == 0) return 0;
-  if (kv_range && doc) return (int)hipErrorInvalidValue;
-  if (D != 64 && D != 128) return (int)hipErrorInvalidValue;
-  if (!offsets_fit(S, ld, ldo)) return (int)hipErrorInvalidValue;
-  const int W = (S + 31) / 32;
-  const uint32_t* mA = (p > 0.f) ? masks : nullptr;
-  const uint32_t* mB = (p > 0.f) ? masks + (size_t)B * H * (32 * W) * W : nullptr;
-  if (p > 0.f && !masks) return (int)hipErrorInvalidValue;
-  dim3 grid((S + 127) / 128, B * H);
-  BwdArgs a{(const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)dout, lse, delta, (const bf16*)o,
-            (bf16*)dq, (bf16*)dk, (bf16*)dv, slopes, mA, mB, B, S, H, ld, ldo, causal, W, scale, p,
-            D == 64 ? bias_part : nullptr, doc ? doc : kv_range};
-  const bool run_dq = g_bwd_kernels & 1, run_dkdv = g_bwd_kernels & 2;
-  if (doc) {
-    if (D == 64) {
-      if (run_dq) hipLaunchKernelGGL((attn_bwd_dq_doc_kernel<64, 3, 64, 1>), grid, dim3(256), 0, s, a);
-      if (run_dkdv) launch_dkdv_doc<64, 2, 128>(grid, s, a);
-    } else {
-      if (run_dq) hipLaunchKernelGGL((attn_bwd_dq_doc_kernel<128, 1, 64, 2>), grid, dim3(256), 0, s, a);
-      if (run_dkdv) launch_dkdv_doc<128, 1, 64>(grid, s, a);
-    }
-    DTD_LAUNCH_CHECK();
-  }
-  if (kv_range) {
-    if (D == 64) {
-      if (run_dq) hipLaunchKernelGGL((attn_bwd_dq_kernel<64, 3, 64, 1, false, true>), grid, dim3(256), 0, s, a);
-      if (run_dkdv) launch_dkdv_range<64, 2, 128>(grid, s, a);
-    } else {
-      if (run_dq) hipLaunchKernelGGL((attn_bwd_dq_kernel<128, 1, 64, 2, false, true>), grid, dim3(256), 0, s, a);
-      if (run_dkdv) launch_dkdv_range<128, 1, 64>(grid, s, a);
-    }
-    DTD_LAUNCH_CHECK();
-  }
+// The plain multi-head backward: a one-kernel form where DTD_ATTN_BWD asks for it and it applies
+// (experimental builds), else the split pair in the forms the environment selects.
+template <int D>
+static void launch_bwd_plain(dim3 grid, bool run_dq, bool run_dkdv, hipStream_t s, const BwdArgs& a) {
 #if DTD_ATTN_FUSED_BWD
-  if (D == 64 && !causal && !slopes && S % 128 == 0 && S <= 512 && bwd_fused()) {
-    const bool drop = mA != nullptr;
-    const dim3 g1(B * H);
+  if (D == 64 && !a.causal && !a.slopes && a.S % 128 == 0 && a.S <= 512 && bwd_fused()) {
+    const bool drop = a.maskA != nullptr;
+    const dim3 g1(a.B * a.H);
     // (the one-key-block-per-wave instantiation, S = 256, gave wrong, run-to-run varying dS rows
     // with dropout on the box -- unresolved, so it is not launched: S = 256 takes the 4-wave form)
-    if (S == 512 && bwd_fused8()) {
+    if (a.S == 512 && bwd_fused8()) {
       if (drop) hipLaunchKernelGGL((attn_bwd_fused8_kernel<2, true>), g1, dim3(512), 0, s, a);
       else hipLaunchKernelGGL((attn_bwd_fused8_kernel<2, false>), g1, dim3(512), 0, s, a);
-      DTD_LAUNCH_CHECK();
+      return;
     }
-    switch (S / 128) {
+    switch (a.S / 128) {
       case 1: if (drop) hipLaunchKernelGGL((attn_bwd_fused_kernel<1, true>), g1, dim3(256), 0, s, a);
               else hipLaunchKernelGGL((attn_bwd_fused_kernel<1, false>), g1, dim3(256), 0, s, a); break;
       case 2: if (drop) hipLaunchKernelGGL((attn_bwd_fused_kernel<2, true>), g1, dim3(256), 0, s, a);
@@ -1739,11 +1745,10 @@ static int attn_bwd_launch(const void* q, const void* k, const void* v, const vo
       default: if (drop) hipLaunchKernelGGL((attn_bwd_fused_kernel<4, true>), g1, dim3(256), 0, s, a);
                else hipLaunchKernelGGL((attn_bwd_fused_kernel<4, false>), g1, dim3(256), 0, s, a); break;
     }
-    DTD_LAUNCH_CHECK();
+    return;
   }
 #endif
-  // dQ first: it also produces delta = rowsum(dO * O), which the dK/dV kernel then reads
-  if (D == 64) {
+  if constexpr (D == 64) {
     const int o = occupancy(2);
     if (!run_dq) {}
     else if (tile_keys(1) == 128) hipLaunchKernelGGL((attn_bwd_dq_kernel<64, 2, 128, 2>), grid, dim3(256), 0, s, a);
@@ -1763,70 +1768,46 @@ static int attn_bwd_launch(const void* q, const void* k, const void* v, const vo
     if (run_dq) hipLaunchKernelGGL((attn_bwd_dq_kernel<128, 1, 64, 2>), grid, dim3(256), 0, s, a);
     if (run_dkdv) launch_dkdv<128, 1, 64>(grid, s, a);
   }
-  DTD_LAUNCH_CHECK();
 }
 
-// Grouped-query backward (see dtd_attn_fwd_gqa): dq holds H heads, dk / dv Hkv heads.  dQ runs on
-// grid (ceil(S/128), B * H) and writes delta, dK/dV then on (ceil(S/128), B * Hkv).
-template <int MODE>
-static void launch_bwd_gqa(int D, dim3 gq, dim3 gkv, hipStream_t s, const BwdArgs& a) {
-  const bool run_dq = g_bwd_kernels & 1, run_dkdv = g_bwd_kernels & 2;
-  if (D == 64) {
-    if (run_dq) hipLaunchKernelGGL((attn_bwd_dq_gqa_kernel<64, 3, 64, 1, MODE>), gq, dim3(256), 0, s, a);
-    if (run_dkdv) hipLaunchKernelGGL((attn_bwd_dkdv_gqa_kernel<64, 2, 128, MODE>), gkv, dim3(256), 0, s, a);
-  } else {
-    if (run_dq) hipLaunchKernelGGL((attn_bwd_dq_gqa_kernel<128, 1, 64, 2, MODE>), gq, dim3(256), 0, s, a);
-    if (run_dkdv) hipLaunchKernelGGL((attn_bwd_dkdv_gqa_kernel<128, 1, 64, MODE>), gkv, dim3(256), 0, s, a);
+// Every other backward: the split pair.  dQ runs on grid gq = (ceil(S/128), B * H), dK/dV on gkv =
+// (ceil(S/128), B * Hkv) -- the grouped forms sum their group's query heads in the accumulators.
+template <int D, int FAM, int MODE>
+static void launch_bwd_form(dim3 gq, dim3 gkv, bool run_dq, bool run_dkdv, hipStream_t s, const BwdArgs& a) {
+  using T = TileForm<D>;
+  if constexpr (FAM == kMha && MODE == 0) return launch_bwd_plain<D>(gq, run_dq, run_dkdv, s, a);
+  if (run_dq) {
+    if constexpr (FAM == kWin) hipLaunchKernelGGL((attn_bwd_dq_win_kernel<D, T::OCC, T::BN, T::RING, MODE>), gq, dim3(256), 0, s, a);
+    else if constexpr (FAM == kGqa) hipLaunchKernelGGL((attn_bwd_dq_gqa_kernel<D, T::OCC, T::BN, T::RING, MODE>), gq, dim3(256), 0, s, a);
+    else if constexpr (MODE == 2) hipLaunchKernelGGL((attn_bwd_dq_doc_kernel<D, T::OCC, T::BN, T::RING>), gq, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((attn_bwd_dq_kernel<D, T::OCC, T::BN, T::RING, false, true>), gq, dim3(256), 0, s, a);
   }
-}
-DTD_EXPORT int dtd_attn_bwd_gqa(const void* q, const void* k, const void* v, const void* o, const void* dout,
-                                const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int S, int H,
-                                int Hkv, int D, int ld, int ldo, int causal, float scale, const int* kv_range,
-                                const int* doc, hipStream_t s) {
-  if (B * S * H == 0) return 0;
-  if (Hkv <= 0 || Hkv >= H || H % Hkv) return (int)hipErrorInvalidValue;
-  if (kv_range && doc) return (int)hipErrorInvalidValue;
-  if (D != 64 && D != 128) return (int)hipErrorInvalidValue;
-  if (!offsets_fit(S, ld, ldo)) return (int)hipErrorInvalidValue;
-  BwdArgs a{(const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)dout, lse, delta, (const bf16*)o,
-            (bf16*)dq, (bf16*)dk, (bf16*)dv, nullptr, nullptr, nullptr, B, S, H, ld, ldo, causal, /*W = */ Hkv, scale,
-            0.f, nullptr, doc ? doc : kv_range};
-  const dim3 gq((S + 127) / 128, B * H), gkv((S + 127) / 128, B * Hkv);
-  if (doc) launch_bwd_gqa<2>(D, gq, gkv, s, a);
-  else if (kv_range) launch_bwd_gqa<1>(D, gq, gkv, s, a);
-  else launch_bwd_gqa<0>(D, gq, gkv, s, a);
-  DTD_LAUNCH_CHECK();
+  if (run_dkdv) {
+    if constexpr (FAM == kWin) hipLaunchKernelGGL((attn_bwd_dkdv_win_kernel<D, T::KV_OCC, T::KV_BM, MODE>), gkv, dim3(256), 0, s, a);
+    else if constexpr (FAM == kGqa) hipLaunchKernelGGL((attn_bwd_dkdv_gqa_kernel<D, T::KV_OCC, T::KV_BM, MODE>), gkv, dim3(256), 0, s, a);
+    else launch_dkdv_masked<D, T::KV_OCC, T::KV_BM, MODE>(gkv, s, a);
+  }
 }
 
-// Sliding-window backward (see dtd_attn_fwd_win): grids as in dtd_attn_bwd_gqa.
-template <int MODE>
-static void launch_bwd_win(int D, dim3 gq, dim3 gkv, hipStream_t s, const BwdArgs& a) {
-  const bool run_dq = g_bwd_kernels & 1, run_dkdv = g_bwd_kernels & 2;
-  if (D == 64) {
-    if (run_dq) hipLaunchKernelGGL((attn_bwd_dq_win_kernel<64, 3, 64, 1, MODE>), gq, dim3(256), 0, s, a);
-    if (run_dkdv) hipLaunchKernelGGL((attn_bwd_dkdv_win_kernel<64, 2, 128, MODE>), gkv, dim3(256), 0, s, a);
-  } else {
-    if (run_dq) hipLaunchKernelGGL((attn_bwd_dq_win_kernel<128, 1, 64, 2, MODE>), gq, dim3(256), 0, s, a);
-    if (run_dkdv) hipLaunchKernelGGL((attn_bwd_dkdv_win_kernel<128, 1, 64, MODE>), gkv, dim3(256), 0, s, a);
-  }
-}
-DTD_EXPORT int dtd_attn_bwd_win(const void* q, const void* k, const void* v, const void* o, const void* dout,
-                                const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int S, int H,
-                                int Hkv, int D, int ld, int ldo, int causal, float scale, int window,
-                                const int* kv_range, const int* doc, hipStream_t s) {
-  if (window <= 0 || !causal) return (int)hipErrorInvalidValue;
-  if (Hkv <= 0 || Hkv > H || H % Hkv) return (int)hipErrorInvalidValue;
-  if (kv_range && doc) return (int)hipErrorInvalidValue;
-  if (D != 64 && D != 128) return (int)hipErrorInvalidValue;
-  if (B * S * H == 0) return 0;
-  if (!offsets_fit(S, ld, ldo)) return (int)hipErrorInvalidValue;
-  BwdArgs a{(const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)dout, lse, delta, (const bf16*)o,
-            (bf16*)dq, (bf16*)dk, (bf16*)dv, nullptr, nullptr, nullptr, B, S, H, ld, ldo, 1, /*W = */ Hkv, scale,
-            /*p = */ window_bits(window < S ? window : S), nullptr, doc ? doc : kv_range};
+// dq/dk/dv: bf16 views with row stride ld into dqkv (dq holds H heads, dk / dv Hkv).  `delta` is
+// [B,H,S] fp32 scratch: the dQ kernel runs first and writes delta = rowsum(dO * O), which the dK/dV
+// kernel then reads.  bias_part: FwdArgs' partials (multi-head, D = 64 only) or nullptr.
+static int attn_bwd_launch(Family fam, const void* q, const void* k, const void* v, const void* o, const void* dout,
+                           const float* lse, float* delta, const uint32_t* masks, void* dq, void* dk, void* dv,
+                           const float* slopes, int B, int S, int H, int Hkv, int D, int ld, int ldo, int causal,
+                           float scale, float p, float* bias_part, int window, const int* kv_range, const int* doc,
+                           hipStream_t s) {
+  if (const int rc = check_call(fam, B, S, H, Hkv, D, ld, ldo, causal, window, kv_range, doc)) return rc < 0 ? 0 : rc;
+  if (p > 0.f && !masks) return (int)hipErrorInvalidValue;
+  const BwdArgs a = bwd_args(q, k, v, o, dout, lse, delta, p > 0.f ? masks : nullptr, dq, dk, dv, slopes, B, S, H, ld, ldo,
+                             causal, scale, p, D == 64 ? bias_part : nullptr, fam == kMha ? 0 : Hkv, window, kv_range, doc);
   const dim3 gq((S + 127) / 128, B * H), gkv((S + 127) / 128, B * Hkv);
-  if (doc) launch_bwd_win<2>(D, gq, gkv, s, a);
-  else if (kv_range) launch_bwd_win<1>(D, gq, gkv, s, a);
-  else launch_bwd_win<0>(D, gq, gkv, s, a);
+  const bool run_dq = g_bwd_kernels & 1, run_dkdv = g_bwd_kernels & 2;
+  with_family(fam, [&](auto f) { with_const<3>(mode_of(kv_range, doc), [&](auto m) {
+    constexpr int FAM = decltype(f)::value, MODE = decltype(m)::value;
+    if (D == 64) launch_bwd_form<64, FAM, MODE>(gq, gkv, run_dq, run_dkdv, s, a);
+    else launch_bwd_form<128, FAM, MODE>(gq, gkv, run_dq, run_dkdv, s, a);
+  }); });
   DTD_LAUNCH_CHECK();
 }
 
@@ -1834,8 +1815,8 @@ DTD_EXPORT int dtd_attn_bwd(const void* q, const void* k, const void* v, const v
                             const float* lse, float* delta, const uint32_t* masks, void* dq, void* dk, void* dv,
                             const float* slopes, int B, int S, int H, int D, int ld, int ldo, int causal, float scale,
                             float p, float* bias_part, hipStream_t s) {
-  return attn_bwd_launch(q, k, v, o, dout, lse, delta, masks, dq, dk, dv, slopes, B, S, H, D, ld, ldo, causal, scale,
-                         p, bias_part, nullptr, nullptr, s);
+  return attn_bwd_launch(kMha, q, k, v, o, dout, lse, delta, masks, dq, dk, dv, slopes, B, S, H, H, D, ld, ldo, causal,
+                         scale, p, bias_part, 0, nullptr, nullptr, s);
 }
 
 // dtd_attn_bwd with a per-sequence key range (kv_range: device int32 [B][2], required)
@@ -1844,8 +1825,8 @@ DTD_EXPORT int dtd_attn_bwd_range(const void* q, const void* k, const void* v, c
                                   const float* slopes, int B, int S, int H, int D, int ld, int ldo, int causal,
                                   float scale, float p, float* bias_part, const int* kv_range, hipStream_t s) {
   if (!kv_range) return (int)hipErrorInvalidValue;
-  return attn_bwd_launch(q, k, v, o, dout, lse, delta, masks, dq, dk, dv, slopes, B, S, H, D, ld, ldo, causal, scale,
-                         p, bias_part, kv_range, nullptr, s);
+  return attn_bwd_launch(kMha, q, k, v, o, dout, lse, delta, masks, dq, dk, dv, slopes, B, S, H, H, D, ld, ldo, causal,
+                         scale, p, bias_part, 0, kv_range, nullptr, s);
 }
 
 // dtd_attn_bwd for a packed batch (doc as in dtd_attn_fwd_doc, required)
@@ -1854,6 +1835,24 @@ DTD_EXPORT int dtd_attn_bwd_doc(const void* q, const void* k, const void* v, con
                                 const float* slopes, int B, int S, int H, int D, int ld, int ldo, int causal,
                                 float scale, float p, float* bias_part, const int* doc, hipStream_t s) {
   if (!doc) return (int)hipErrorInvalidValue;
-  return attn_bwd_launch(q, k, v, o, dout, lse, delta, masks, dq, dk, dv, slopes, B, S, H, D, ld, ldo, causal, scale,
-                         p, bias_part, nullptr, doc, s);
+  return attn_bwd_launch(kMha, q, k, v, o, dout, lse, delta, masks, dq, dk, dv, slopes, B, S, H, H, D, ld, ldo, causal,
+                         scale, p, bias_part, 0, nullptr, doc, s);
+}
+
+// Grouped-query backward (see dtd_attn_fwd_gqa)
+DTD_EXPORT int dtd_attn_bwd_gqa(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                                const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int S, int H,
+                                int Hkv, int D, int ld, int ldo, int causal, float scale, const int* kv_range,
+                                const int* doc, hipStream_t s) {
+  return attn_bwd_launch(kGqa, q, k, v, o, dout, lse, delta, nullptr, dq, dk, dv, nullptr, B, S, H, Hkv, D, ld, ldo,
+                         causal, scale, 0.f, nullptr, 0, kv_range, doc, s);
+}
+
+// Sliding-window backward (see dtd_attn_fwd_win)
+DTD_EXPORT int dtd_attn_bwd_win(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                                const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int S, int H,
+                                int Hkv, int D, int ld, int ldo, int causal, float scale, int window,
+                                const int* kv_range, const int* doc, hipStream_t s) {
+  return attn_bwd_launch(kWin, q, k, v, o, dout, lse, delta, nullptr, dq, dk, dv, nullptr, B, S, H, Hkv, D, ld, ldo,
+                         causal, scale, 0.f, nullptr, window, kv_range, doc, s);
 }

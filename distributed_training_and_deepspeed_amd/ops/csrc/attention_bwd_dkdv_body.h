@@ -22,14 +22,14 @@
   int tx, ty;
   if constexpr (RANGE || DOC) xcd_tile_grouped(tx, ty);
   else xcd_tile(tx, ty);
-  // GQA: grid y = B * Hkv (Hkv rides in a.W: the GQA forms run without dropout).  The workgroup
+  // GQA: grid y = B * Hkv (Hkv = a.hkv(), see FwdArgs).  The workgroup
   // owns key/value head hk of sequence b and walks the query tiles of its G = H / Hkv query heads
   // hk * G .. hk * G + G - 1 in turn; `h` / `bh` name the query head whose tile is being fetched.
   int bh = ty, b = bh / a.H, h = bh % a.H, hk = h, G = 1;
   if constexpr (GQA) {
-    b = ty / a.W;
-    hk = ty % a.W;
-    G = a.H / a.W;
+    b = ty / a.hkv();
+    hk = ty % a.hkv();
+    G = a.H / a.hkv();
     h = hk * G;
     bh = b * a.H + h;
   }
@@ -39,7 +39,7 @@
   const bool kvalid = key < S;
   int klo = 0, khi = S;
   // DOC: (klo, khi) are the block's document bounds = the queries that may see one of its keys
-  if constexpr (DOC) load_block_range(a.kv_range, a.B, b, gridDim.x, tx, S, klo, khi);
+  if constexpr (DOC) load_block_range(a.doc(), a.B, b, gridDim.x, tx, S, klo, khi);
   if constexpr (RANGE || DOC) {
     if constexpr (RANGE) load_range(a.kv_range, b, S, klo, khi);
     // block-uniform: no key of this block is in the range (DOC: every key of it is a pad)
@@ -63,12 +63,11 @@
   }
   const bool kin = key >= klo && key < khi;     // this lane's key takes part (RANGE)
   SpanOf<DOC> doc{};                            // this lane's key's document = its valid queries (DOC)
-  if constexpr (DOC) doc = load_span(a.kv_range, b, S, key);
-  // WIN: key j is seen by the queries j <= q < j + win (the window rides in a.p, see
-  // attention_fwd_body.h); a span takes that end in
+  if constexpr (DOC) doc = load_span(a.doc(), b, S, key);
+  // WIN: key j is seen by the queries j <= q < j + win (a.window(), see FwdArgs); a span takes that end in
   int win = 0;
   if constexpr (WIN) {
-    win = __builtin_amdgcn_readfirstlane(__float_as_int(a.p));
+    win = __builtin_amdgcn_readfirstlane(a.window());
     if constexpr (DOC) doc.clip_hi(key + win);
   }
   const float sl2 = a.slopes ? a.slopes[h] * kLog2e : 0.f;

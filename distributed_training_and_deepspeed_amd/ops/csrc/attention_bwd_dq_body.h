@@ -16,8 +16,8 @@
   const int qblk = tx * 128, q0 = qblk + w * 32;
   const int q = q0 + r;
   const bool qvalid = q < S;
-  int hk = h;   // GQA: the key/value head h / G (Hkv rides in a.W, see attention_fwd_body.h)
-  if constexpr (GQA) hk = __builtin_amdgcn_readfirstlane(h / (a.H / a.W));
+  int hk = h;   // GQA: the key/value head h / G (a.hkv(), see FwdArgs)
+  if constexpr (GQA) hk = __builtin_amdgcn_readfirstlane(h / (a.H / a.hkv()));
   const float sl2 = a.slopes ? a.slopes[h] * kLog2e : 0.f;
   const float sc2 = a.scale * kLog2e;
   const bool drop = a.maskA != nullptr;
@@ -38,12 +38,12 @@
   if constexpr (RANGE) load_range(a.kv_range, b, S, klo, khi);
   SpanOf<DOC> doc{};
   if constexpr (DOC) {
-    load_block_range(a.kv_range, a.B, b, gridDim.x, tx, S, klo, khi);
-    doc = load_span(a.kv_range, b, S, q);
+    load_block_range(a.doc(), a.B, b, gridDim.x, tx, S, klo, khi);
+    doc = load_span(a.doc(), b, S, q);
   }
   int win = 0;   // WIN: the sliding window, folded into the tile range and the span as in attn_fwd_kernel
   if constexpr (WIN) {
-    win = __builtin_amdgcn_readfirstlane(__float_as_int(a.p));
+    win = __builtin_amdgcn_readfirstlane(a.window());
     klo = max(klo, qblk - win + 1);
     if constexpr (DOC) doc.clip_lo(q - win + 1);
   }

@@ -22,9 +22,9 @@
   const int q = q0 + r;
   const bool qvalid = q < S;
   // GQA: K/V come from head h / G (G = H / Hkv query heads per key/value head; the GQA forms run
-  // without dropout, so the argument block's keep-word count W carries Hkv); workgroup-uniform
+  // without dropout, so the argument block carries Hkv where the keep-word count was: FwdArgs::hkv); workgroup-uniform
   int hk = h;
-  if constexpr (GQA) hk = __builtin_amdgcn_readfirstlane(h / (a.H / a.W));
+  if constexpr (GQA) hk = __builtin_amdgcn_readfirstlane(h / (a.H / a.hkv()));
   const float sl2 = a.slopes ? a.slopes[h] * kLog2e : 0.f;
   const float sc2 = a.scale * kLog2e;
   const bool drop = a.maskA != nullptr;
@@ -57,15 +57,15 @@
   // DOC: the block's bounds take the range's place; the lane's own span does the masking
   SpanOf<DOC> doc{};
   if constexpr (DOC) {
-    load_block_range(a.kv_range, a.B, b, gridDim.x, tx, S, klo, khi);
-    doc = load_span(a.kv_range, b, S, q);
+    load_block_range(a.doc(), a.B, b, gridDim.x, tx, S, klo, khi);
+    doc = load_span(a.doc(), b, S, q);
   }
   // WIN: query q sees key j iff q - win < j <= q (the windowed forms run causal, without dropout, so
-  // the argument block's p carries the window as an integer).  The block's first key is that of its
+  // the argument block carries the window: FwdArgs::window).  The block's first key is that of its
   // first query, so the tile range starts there; a span takes the window in at no cost.
   int win = 0;
   if constexpr (WIN) {
-    win = __builtin_amdgcn_readfirstlane(__float_as_int(a.p));
+    win = __builtin_amdgcn_readfirstlane(a.window());
     klo = max(klo, qblk - win + 1);
     if constexpr (DOC) doc.clip_lo(q - win + 1);
   }
