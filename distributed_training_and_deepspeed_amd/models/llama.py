@@ -29,7 +29,11 @@ Sliding window (``cfg.sliding_window`` = W > 0, Mistral): query i attends the W 
 intersected with the key range / document span.  The fused path hands W to the attention kernels
 (ops/attention.py, ``window``), which visit only the band's tiles; the reference masks the band.
 
-Rotary scaling and a KV cache are not implemented.
+Incremental decoding (``forward_cached``): the layer with a KV cache ``[B, Hkv, Smax, D]`` per layer
+(ops/kv_cache.py) -- the prompt through the training forward's attention, then one token per step through
+the split-KV decode kernel (ops/csrc/attention_decode.hip); ``CausalLM.generate`` drives it.
+
+Rotary scaling is not implemented.
 """
 from __future__ import annotations
 
@@ -118,6 +122,54 @@ class LlamaLayer(nn.Module):
             note_use(self.params())
             return _FusedLlamaLayerFn.apply(x, self, key_range, doc_range, position_ids, table, *self.params())
         return self._reference(x, key_range, doc_range, position_ids, table)
+
+    # ------------------------------------------------------------------ incremental decoding
+    @torch.no_grad()
+    def forward_cached(self, x: torch.Tensor, cache, i: int, prefill: bool,
+                       key_range: torch.Tensor | None = None) -> torch.Tensor:
+        """x [B, Sq, h] -> [B, Sq, h] with the KV cache (ops/kv_cache.py) as layer ``i``; no autograd node.
+        The new tokens sit at the slots ``cache.kv_len[b] + s``, which are also their rotary positions; the
+        rotated k rows and the v rows are appended there (``Fx.rope_append_``) and ``cache.kv_len`` is left
+        alone -- the caller advances it after the last layer.  ``prefill``: the prompt into an empty cache,
+        attention being the training forward's over the prompt itself (``key_range`` for a left-padded
+        one).  Otherwise one token per sequence (Sq = 1) against the cache (``A.attn_decode``).  The fused
+        path runs the kernels of the training forward around it; the reference path the same cache in
+        plain PyTorch."""
+        c, rt = self.cfg, self.rt
+        B, Sq, h = x.shape
+        H, D, Hkv = c.num_heads, c.head_dim, c.kv_heads
+        if not prefill and Sq != 1:
+            raise ValueError(f"a decode step takes one token per sequence, got {Sq}")
+        table = rope_table_for(rt, c, x.device)
+        kc, vc = cache.layer(i)
+        fused = rt.use_fused(x)
+        eps, window = c.ln_eps, c.sliding_window or None
+        x2d = x.reshape(B * Sq, h)
+        if fused:
+            _, a_in, _ = Fx.rms_fwd(None, x2d, self.n1_g, eps)
+            qkv = _linear(a_in, self.qkv_w)
+        else:
+            qkv = F.linear(ref_rms_norm(x2d, self.n1_g, eps), self.qkv_w)
+        Fx.rope_append_(qkv, table, kc, vc, cache.kv_len, B, Sq, H, D, kv_heads=Hkv, overflow=cache.overflow)
+        if prefill:
+            attn = A.attn_fwd if fused else A.attn_fwd_ref
+            actx = attn(qkv, B, Sq, H, D, c.causal, key_range=key_range, kv_heads=Hkv if Hkv != H else None,
+                        window=window)[0]
+        elif fused:
+            actx, _ = A.attn_decode(qkv, kc, vc, cache.kv_next, B, H, D, Hkv, window, cache.kv_start,
+                                    splits=cache.splits, workspace=cache.workspace)
+        else:
+            actx, _ = A.attn_decode_ref(qkv, kc, vc, cache.kv_next, B, H, D, Hkv, window, cache.kv_start)
+        if fused:
+            o = _linear(actx, self.o_w)
+            z1, f_in, _ = Fx.rms_fwd(o, x2d, self.n2_g, eps)
+            a = Fx.swiglu_fwd(_linear(f_in, self.gu_w))
+            out = Fx.dropout_add(_linear(a, self.down_w), z1, 0.0, rt.rng, 0)
+        else:
+            z1 = x2d + F.linear(actx, self.o_w)
+            g, u = F.linear(ref_rms_norm(z1, self.n2_g, eps), self.gu_w).split(c.ffn_size, -1)
+            out = z1 + F.linear(F.silu(g) * u, self.down_w)
+        return out.view(B, Sq, h)
 
     # ------------------------------------------------------------------ reference path
     def _reference(self, x, key_range, doc_range, position_ids, table):

@@ -102,6 +102,12 @@ _SIGS = {
     "dtd_attn_set_bwd_form": (I, [I]),
     "dtd_attn_set_bwd_kernels": (I, [I]),
     "dtd_attn_fused_bwd_built": (I, []),
+    # attention_decode.hip (q, ldq, k, v, kv_len, kv_start or null, ctx, ldo, lse, ws, ws floats, B, H, Hkv, D,
+    # Smax, window, scale, splits | dtype, qkv, table, k cache, v cache, kv_len, overflow, B, Sq, H, Hkv, D, ld,
+    # Smax, table positions)
+    "dtd_attn_decode_key_tile": (I, []),
+    "dtd_attn_decode": (I, [P, L, P, P, P, P, P, L, P, P, L, I, I, I, I, I, I, F, I, P]),
+    "dtd_rope_append": (I, [I, P, P, P, P, P, P, I, I, I, I, I, L, I, I, P]),
     # attention_f32.hip
     "dtd_attn_fwd_f32": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, F, P]),
     "dtd_attn_bwd_f32": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, F, P]),

@@ -41,6 +41,9 @@ visit only the O(S W) band of key tiles; the multi-head layout runs through them
 per group (its q | k | v blocks are that layout).  ``window`` None, 0 or >= S is the call without
 the argument, on its code paths and bit for bit.
 
+Incremental decoding (``attn_decode``, at the end of this module): one new query per sequence against a
+KV cache ``[B, Hkv, Smax, D]`` whose fill level lives in device memory (ops/kv_cache.py).
+
 Reference semantics: HF BertSelfAttention eager path (matmul, softmax, dropout, matmul --
 SURVEY.md K2, reference model/transformer.py:80-86); the reference never passes an
 attention mask for BERT (data_parallel_training.py:53), so by default (no ``key_range``) padding
@@ -687,3 +690,143 @@ def attn_bwd(dctx, qkv, ctx, lse, B, S, H, D, causal=False, slopes=None, p=0.0, 
     elif dbias is not None:
         Fx.bias_grad(dqkv, *dbias)
     return dqkv
+
+
+# ---------------------------------------------------------------------------------- incremental decoding
+# One new query token per sequence against a KV cache (ops/kv_cache.py, ops/csrc/attention_decode.hip).
+# Cache layout, per layer: K, V [B, Hkv, Smax, D]; ``kv_len`` / ``kv_start`` are device int32 [B] (slots
+# written, counting the new token; first valid slot, 0 unless the prompt was left-padded).  Sequence b
+# attends the slots max(kv_start[b], hi - W) <= j < hi with hi = min(kv_len[b], Smax) -- a kv_len beyond
+# the cache is clamped, not trusted, before the window is applied; an empty range gives ctx = 0,
+# lse = -inf (the empty-row rule above).
+DECODE_KEY_TILE = 64          # keys per tile of the decode kernel: split boundaries are its multiples
+_DECODE_MAX_GROUP = 8         # query heads per key/value head the kernel keeps in registers
+_DECODE_WORKGROUPS = 512      # two workgroups for each of the 256 CUs
+
+
+def decode_splits(B: int, Hkv: int, Smax: int) -> int:
+    """Key splits of a decode call: a function of (B, Hkv, Smax) only -- never of the cache position --
+    so the launch sequence of a step is static and can be captured.  Enough (sequence, key/value head,
+    split) workgroups to cover the CUs twice, but no split shorter than two key tiles."""
+    tiles = (Smax + DECODE_KEY_TILE - 1) // DECODE_KEY_TILE
+    want = (_DECODE_WORKGROUPS + B * Hkv - 1) // max(1, B * Hkv)
+    return max(1, min(want, tiles // 2))
+
+
+def decode_workspace_floats(B: int, H: int, D: int, splits: int) -> int:
+    """fp32 elements of the decode kernel's split workspace: (m, l, o[D]) per (split, sequence, head)."""
+    return splits * B * H * (D + 2)
+
+
+def _decode_bounds(kv_len, kv_start, window, Smax):
+    """(lo, hi) int64 [B] of a decode call (see above)."""
+    hi = kv_len.to(torch.int64).clamp(max=Smax)
+    lo = torch.zeros_like(hi) if kv_start is None else kv_start.to(device=hi.device, dtype=torch.int64).clamp(min=0)
+    if window:
+        lo = torch.maximum(lo, hi - int(window))
+    return lo, hi
+
+
+def _decode_window(window) -> int:
+    if window is None:
+        return 0
+    if isinstance(window, bool) or int(window) != window or window < 0:
+        raise ValueError(f"window must be a positive integer (or None / 0 for no window), got {window!r}")
+    return int(window)
+
+
+def _check_decode(qkv, k_cache, v_cache, kv_len, B, H, Hkv, D):
+    if qkv.dim() != 2 or tuple(qkv.shape) != (B, (H + 2 * Hkv) * D) or qkv.stride(1) != 1:
+        raise ValueError(f"qkv must be [B, (H + 2*Hkv)*D] = [{B}, {(H + 2 * Hkv) * D}], got {tuple(qkv.shape)}")
+    if k_cache.dim() != 4 or tuple(k_cache.shape[:2]) != (B, Hkv) or k_cache.shape[3] != D \
+            or v_cache.shape != k_cache.shape:
+        raise ValueError(f"k_cache / v_cache must be [B, Hkv, Smax, D] = [{B}, {Hkv}, Smax, {D}], got "
+                         f"{tuple(k_cache.shape)} / {tuple(v_cache.shape)}")
+    if k_cache.dtype != qkv.dtype or v_cache.dtype != qkv.dtype:
+        raise ValueError("the cache must have the activations' dtype")
+    if kv_len.numel() != B:
+        raise ValueError(f"kv_len must hold one length per sequence ({B}), got {tuple(kv_len.shape)}")
+
+
+def attn_decode_ref(qkv, k_cache, v_cache, kv_len, B, H, D, kv_heads=None, window=None, kv_start=None, scale=None):
+    """Math reference of ``attn_decode``: plain PyTorch over the whole cache with the slots outside
+    [lo, hi) masked, softmax in fp32 (fp64 for fp64 inputs), the rounding points of ``attn_fwd_ref``
+    (ctx rounded once, at the end).  Returns (ctx [B, H*D], lse [B, H] fp32)."""
+    Hkv = _kv_heads(kv_heads, H)
+    _check_decode(qkv, k_cache, v_cache, kv_len, B, H, Hkv, D)
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    Smax = k_cache.shape[2]
+    c = _cdt(qkv)
+    q = qkv[:, :H * D].reshape(B, H, 1, D).to(c)
+    G = H // Hkv
+    k, v = k_cache.to(c).repeat_interleave(G, 1), v_cache.to(c).repeat_interleave(G, 1)     # [B, H, Smax, D]
+    s = torch.matmul(q, k.transpose(-1, -2)) * scale                                       # [B, H, 1, Smax]
+    lo, hi = _decode_bounds(kv_len.to(qkv.device), kv_start, _decode_window(window), Smax)
+    j = torch.arange(Smax, device=qkv.device).view(1, Smax)
+    outside = ((j < lo.view(B, 1)) | (j >= hi.view(B, 1))).view(B, 1, 1, Smax)
+    s = s.masked_fill(outside, float("-inf"))
+    lse = torch.logsumexp(s, -1)
+    prob = _probs(s, lse)
+    # (0 * a masked slot's V: a never-written slot may hold anything, NaN included -- it takes no part)
+    v = v.masked_fill(outside.transpose(-1, -2), 0.0)
+    ctx = torch.matmul(prob, v)                                                            # [B, H, 1, D]
+    return ctx.reshape(B, H * D).to(qkv.dtype), lse.reshape(B, H).to(torch.float32)
+
+
+def decode_kernel_supported(qkv: torch.Tensor, H: int, Hkv: int, D: int) -> bool:
+    """The decode kernel's domain: bf16 on the GPU, D 64 / 128, at most 8 query heads per key/value head."""
+    return qkv.is_cuda and qkv.dtype == torch.bfloat16 and D in (64, 128) and H // Hkv <= _DECODE_MAX_GROUP
+
+
+def attn_decode(qkv, k_cache, v_cache, kv_len, B, H, D, kv_heads=None, window=None, kv_start=None, splits=None,
+                workspace: torch.Tensor | None = None, out: tuple | None = None):
+    """Attention of one new token per sequence against the cache: ``qkv [B, (H + 2*Hkv)*D]`` is the step's
+    packed projection output (only its q block is read; its k / v rows are already in the cache,
+    ``functional.rope_append_``), ``k_cache`` / ``v_cache [B, Hkv, Smax, D]``, ``kv_len`` / ``kv_start``
+    device int32 [B] as above.  Returns (ctx [B, H*D], lse [B, H] fp32).
+
+    One routing rule: bf16 on the GPU with D 64 / 128 and H / Hkv <= 8 runs the split-KV kernel (a library
+    without it is an error, not a fallback); everything else -- larger groups, fp32, the CPU -- the math
+    reference.  ``splits``: override of ``decode_splits`` (tests, benchmarks).  ``workspace``: fp32 buffer of
+    at least ``decode_workspace_floats`` elements (``KVCache`` holds one, so a captured step allocates
+    nothing for it); allocated here when None.  ``out``: (ctx, lse) tensors to write, of the returned
+    shapes and dtypes, ctx with unit column stride."""
+    Hkv = _kv_heads(kv_heads, H)
+    window = _decode_window(window)
+    _check_decode(qkv, k_cache, v_cache, kv_len, B, H, Hkv, D)
+    if not decode_kernel_supported(qkv, H, Hkv, D):
+        ctx, lse = attn_decode_ref(qkv, k_cache, v_cache, kv_len, B, H, D, Hkv, window, kv_start)
+        if out is not None:
+            out[0].copy_(ctx)
+            out[1].copy_(lse)
+            return out[0], out[1]
+        return ctx, lse
+    _require("dtd_attn_decode", "decode")
+    Smax = k_cache.shape[2]
+    if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise ValueError("k_cache / v_cache must be contiguous [B, Hkv, Smax, D]")
+    tiles = (Smax + DECODE_KEY_TILE - 1) // DECODE_KEY_TILE
+    splits = decode_splits(B, Hkv, Smax) if splits is None else int(splits)
+    if splits < 1:
+        raise ValueError(f"splits must be >= 1, got {splits}")
+    splits = min(splits, tiles)
+    need = decode_workspace_floats(B, H, D, splits)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float32, device=qkv.device)
+    elif workspace.dtype != torch.float32 or workspace.numel() < need or not workspace.is_contiguous():
+        raise ValueError(f"workspace must be a contiguous fp32 tensor of at least {need} elements")
+    dev = qkv.device
+    kv_len = kv_len.to(device=dev, dtype=torch.int32).contiguous()
+    kv_start = kv_start.to(device=dev, dtype=torch.int32).contiguous() if kv_start is not None else None
+    if out is None:
+        ctx = torch.empty((B, H * D), dtype=qkv.dtype, device=dev)
+        lse = torch.empty((B, H), dtype=torch.float32, device=dev)
+    else:
+        ctx, lse = out
+        if tuple(ctx.shape) != (B, H * D) or ctx.dtype != qkv.dtype or ctx.stride(1) != 1 or ctx.device != dev \
+                or tuple(lse.shape) != (B, H) or lse.dtype != torch.float32 or not lse.is_contiguous() or lse.device != dev:
+            raise ValueError(f"out must be (ctx [{B}, {H * D}] {qkv.dtype}, lse [{B}, {H}] fp32, contiguous) on {dev}")
+    _lib.call("dtd_attn_decode", qkv.data_ptr(), qkv.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
+              kv_len.data_ptr(), _lib.ptr(kv_start), ctx.data_ptr(), ctx.stride(0), lse.data_ptr(), workspace.data_ptr(),
+              workspace.numel(), B, H, Hkv, D, Smax, window, 1.0 / math.sqrt(D), splits, _lib.stream())
+    return ctx, lse

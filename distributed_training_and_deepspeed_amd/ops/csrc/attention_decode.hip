@@ -1,0 +1,398 @@
+// Incremental decoding: the KV-cache append (with the rotary embedding) and single-query attention
+// against the cache.
+//
+// Cache layout, per layer: K, V [B, Hkv, Smax, D] in the model's dtype -- the keys of one (sequence,
+// key/value head) are one contiguous stream of D-element rows.  Two device int32 [B] arrays are shared
+// by all layers: kv_len (slots written) and kv_start (first valid slot, 0 unless the prompt was
+// left-padded).  Nothing about the cache position is read back to the host: both kernels take the
+// arrays as pointers, so their launch sequence is static and can be captured into a graph.
+//
+// dtd_rope_append: rope.hip's rotation (same table, same expression, same rounding) in place on the q
+// and k heads of a packed qkv [B*Sq, (H + 2 Hkv) D] with position kv_len[b] + s, plus the copy of the
+// rotated k row and of the v row of token (b, s) into slot kv_len[b] + s.  A slot outside [0, Smax) is
+// not written and raises the overflow flag (a plain vector store of 1).  kv_len is not advanced here.
+//
+// dtd_attn_decode: one query token per sequence; sequence b attends the slots
+//     max(kv_start[b], hi - W) <= j < hi,   hi = min(kv_len[b], Smax)     (W = 0: no window),
+// kv_len already counting the new token.  An empty range gives ctx = 0, lse = -inf.  Split-KV in two
+// launches, no atomics, a fixed summation order (two calls are bitwise equal):
+//   * decode_split_kernel, grid (splits, Hkv, B), 256 threads: one workgroup owns the keys
+//     [split * kps, (split + 1) * kps) of one (sequence, key/value head), kps a multiple of the 64-key
+//     tile, for all G = H / Hkv query heads of the group -- K / V are read once per group.  This is a
+//     GEMV-shaped HBM stream, so K / V rows go straight into VGPRs with 16-byte loads (D / 8 lanes per
+//     row, 64 / (D / 8) rows per wave and load instruction, the next tile's loads issued before the
+//     current tile's arithmetic) and never through LDS.  The scores are packed-bf16 dot products reduced
+//     over a row's lanes with DPP adds; the online-softmax state (m, l, o) is fp32 per query head and per
+//     lane group.  LDS serves only the reduction over the lane groups at the end, which writes the
+//     split's fp32 partial (m in log2 units, l, o[D]) per query head into the workspace
+//     ws [splits][B][H][D + 2].  A split without a key writes (-inf, 0, 0) and returns.
+//   * decode_combine_kernel, grid (H, B), D threads: merges the splits in index order, writes ctx in
+//     the model's dtype and lse.
+// Every load address is clamped into [lo, hi), hi <= Smax, so no slot outside the cache -- and no slot
+// that was never written -- is read, whatever kv_len / kv_start hold.  All index arithmetic is 64-bit.
+#include "common.h"
+
+using namespace dtd;
+
+namespace {
+
+constexpr int kKeyTile = 64;
+constexpr int kMaxGroup = 8;
+constexpr float kLog2e = 1.4426950408889634f;
+constexpr float kLn2 = 0.6931471805599453f;
+
+// ---------------------------------------------------------------------------------- rope + append
+template <typename T>
+__global__ void __launch_bounds__(256) rope_append_kernel(T* __restrict__ qkv, const float* __restrict__ table,
+                                                          T* __restrict__ kc, T* __restrict__ vc,
+                                                          const int* __restrict__ kv_len, int* __restrict__ overflow,
+                                                          size_t items, int Sq, int H, int Hkv, int D, size_t ld,
+                                                          int Smax, int max_pos, float sgn) {
+  const int vph = D >> 4;            // 8-wide vectors per half head
+  const int half = D >> 1;
+  const int heads = H + 2 * Hkv;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < items; i += (size_t)gridDim.x * blockDim.x) {
+    const int v = (int)(i % vph);
+    const size_t hr = i / vph;
+    const int hd = (int)(hr % heads);
+    const size_t row = hr / heads;
+    const size_t b = row / (size_t)Sq;
+    const long long slot = (long long)kv_len[b] + (long long)(row % (size_t)Sq);
+    const bool fits = slot >= 0 && slot < (long long)Smax;
+    T* x = qkv + row * ld + (size_t)hd * D + v * 8;
+    float oa[8], ob[8];
+    if (hd < H + Hkv) {              // a q or k head: rotate in place (rope.hip's expression)
+      int p = slot < 0 ? 0 : (slot >= (long long)max_pos ? max_pos - 1 : (int)slot);
+      const float* cs = table + ((size_t)p * half + v * 8) * 2;
+      float a[8], bb[8], t[16];
+      vload<T, 8>(x, a);
+      vload<T, 8>(x + half, bb);
+      vload<float, 16>(cs, t);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        // rope.hip writes a * c - b * sn and b * c + a * sn and its compiled form contracts the first
+        // product of each: spelled out here, so that the two kernels round alike whatever the
+        // vectoriser makes of this loop
+        const float c = t[2 * j], sn = sgn * t[2 * j + 1];
+        oa[j] = __builtin_fmaf(a[j], c, -(bb[j] * sn));
+        ob[j] = __builtin_fmaf(bb[j], c, a[j] * sn);
+      }
+      vstore<T, 8>(x, oa);
+      vstore<T, 8>(x + half, ob);
+      if (hd < H) continue;
+    } else {
+      vload<T, 8>(x, oa);
+      vload<T, 8>(x + half, ob);
+    }
+    if (!fits) {
+      *overflow = 1;
+      continue;
+    }
+    const int hk = hd < H + Hkv ? hd - H : hd - H - Hkv;
+    T* dst = (hd < H + Hkv ? kc : vc) + ((b * (size_t)Hkv + hk) * (size_t)Smax + (size_t)slot) * D + v * 8;
+    vstore<T, 8>(dst, oa);
+    vstore<T, 8>(dst + half, ob);
+  }
+}
+
+// ---------------------------------------------------------------------------------- decode attention
+struct DecodeArgs {
+  const bf16* q;      // the q block of the step's qkv: row b at q + b * ldq, head h at column h * D
+  const bf16* k;      // [B, Hkv, Smax, D]
+  const bf16* v;
+  const int* kv_len;
+  const int* kv_start;   // or nullptr
+  float* ws;          // [splits][B][H][D + 2]
+  long long ldq;
+  int B, H, Hkv, G, Smax, window, kps;
+  float scale2;       // scale * log2(e): the scores are kept in log2 units
+};
+
+template <int CTRL>
+__device__ __forceinline__ float dpp_f(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
+}
+
+// Sum over the LPK (8 or 16) lanes that hold one key row; every lane gets the sum.
+template <int LPK>
+__device__ __forceinline__ float row_sum(float v) {
+  v += dpp_f<0xB1>(v);     // quad_perm [1, 0, 3, 2]
+  v += dpp_f<0x4E>(v);     // quad_perm [2, 3, 0, 1]
+  v += dpp_f<0x141>(v);    // row_half_mirror: the other quad of the 8
+  if constexpr (LPK == 16) v += dpp_f<0x140>(v);   // row_mirror: the other half of the 16
+  return v;
+}
+
+__device__ __forceinline__ float fexp2(float x) { return __builtin_amdgcn_exp2f(x); }
+
+__device__ __forceinline__ float dot8(const bf16x8 a, const bf16x2 (&q)[4]) {
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    bf16x2 p;
+    p[0] = a[2 * i];
+    p[1] = a[2 * i + 1];
+#if __has_builtin(__builtin_amdgcn_fdot2_f32_bf16)
+    s = __builtin_amdgcn_fdot2_f32_bf16(p, q[i], s, false);
+#else
+    s += (float)p[0] * (float)q[i][0] + (float)p[1] * (float)q[i][1];
+#endif
+  }
+  return s;
+}
+
+template <int D>
+__device__ __forceinline__ void write_empty(const DecodeArgs& a, int split, int b, int hk) {
+  for (int idx = threadIdx.x; idx < a.G * (D + 2); idx += blockDim.x) {
+    const int g = idx / (D + 2), e = idx - g * (D + 2);
+    const size_t base = (((size_t)split * a.B + b) * a.H + (size_t)hk * a.G + g) * (D + 2);
+    a.ws[base + e] = e == 0 ? -INFINITY : 0.f;
+  }
+}
+
+// GP: the group size G rounded up to a power of two (heads g >= G carry zeros and are not written).
+template <int D, int GP>
+__global__ void __launch_bounds__(256) decode_split_kernel(const DecodeArgs a) {
+  constexpr int LPK = D / 8;             // lanes per key row (16 bytes each)
+  constexpr int GPW = 64 / LPK;          // key rows per wave and load instruction
+  constexpr int NG = 4 * GPW;            // lane groups per workgroup
+  constexpr int KPG = kKeyTile / NG;     // keys per lane group and tile
+  constexpr int HC = GP < 4 ? GP : 4;    // query heads per pass of the final reduction
+  __shared__ __attribute__((aligned(16))) float so[HC][NG][D];
+  __shared__ float sm[HC][NG], sl[HC][NG];
+
+  const int split = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int sub = lane % LPK;
+  const int grp = wave * GPW + lane / LPK;
+  const int G = a.G;
+
+  int hi = a.kv_len[b];
+  hi = hi < a.Smax ? hi : a.Smax;
+  int lo = a.kv_start ? a.kv_start[b] : 0;
+  lo = lo > 0 ? lo : 0;
+  if (a.window > 0 && hi - a.window > lo) lo = hi - a.window;
+  const int k0 = split * a.kps;
+  const int k1 = k0 + a.kps < hi ? k0 + a.kps : hi;
+  const int lot = lo / kKeyTile * kKeyTile;
+  const int t0 = k0 > lot ? k0 : lot;    // both multiples of the tile
+  if (lo >= hi || t0 >= k1) {            // no key of this split takes part
+    write_empty<D>(a, split, b, hk);
+    return;
+  }
+
+  bf16x2 q[GP][4];
+#pragma unroll
+  for (int g = 0; g < GP; ++g) {
+    bf16x8 x = {};
+    if (g < G) x = *reinterpret_cast<const bf16x8*>(a.q + (size_t)b * a.ldq + ((size_t)hk * G + g) * D + sub * 8);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      q[g][i][0] = x[2 * i];
+      q[g][i][1] = x[2 * i + 1];
+    }
+  }
+  float m[GP], l[GP], o[GP][8];
+#pragma unroll
+  for (int g = 0; g < GP; ++g) {
+    m[g] = -INFINITY;
+    l[g] = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[g][e] = 0.f;
+  }
+
+  const size_t head = ((size_t)b * a.Hkv + hk) * (size_t)a.Smax * D + sub * 8;
+  const bf16* Kb = a.k + head;
+  const bf16* Vb = a.v + head;
+  const int last = hi - 1;               // lo <= last here: every address stays inside [lo, hi), hi <= Smax
+
+  bf16x8 kk[KPG], vv[KPG];
+#pragma unroll
+  for (int i = 0; i < KPG; ++i) {
+    int j = t0 + i * NG + grp;
+    j = j < last ? j : last;
+    j = j > lo ? j : lo;                 // a masked slot reads a live one: never-written rows may hold NaN
+    kk[i] = *reinterpret_cast<const bf16x8*>(Kb + (size_t)j * D);
+    vv[i] = *reinterpret_cast<const bf16x8*>(Vb + (size_t)j * D);
+  }
+  for (int t = t0; t < k1; t += kKeyTile) {
+    bf16x8 kn[KPG], vn[KPG];
+    const int tn = t + kKeyTile < k1 ? t + kKeyTile : t;     // (the last tile is loaded twice: in bounds)
+#pragma unroll
+    for (int i = 0; i < KPG; ++i) {
+      int j = tn + i * NG + grp;
+      j = j < last ? j : last;
+      j = j > lo ? j : lo;
+      kn[i] = *reinterpret_cast<const bf16x8*>(Kb + (size_t)j * D);
+      vn[i] = *reinterpret_cast<const bf16x8*>(Vb + (size_t)j * D);
+    }
+    float vf[KPG][8];
+    bool ok[KPG];
+#pragma unroll
+    for (int i = 0; i < KPG; ++i) {
+      const int j = t + i * NG + grp;
+      ok[i] = j >= lo && j < hi;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) vf[i][e] = (float)vv[i][e];
+    }
+#pragma unroll
+    for (int g = 0; g < GP; ++g) {
+      float s[KPG];
+      float mn = m[g];
+#pragma unroll
+      for (int i = 0; i < KPG; ++i) {
+        const float d = row_sum<LPK>(dot8(kk[i], q[g])) * a.scale2;
+        s[i] = ok[i] ? d : -INFINITY;
+        mn = fmaxf(mn, s[i]);
+      }
+      const float ms = mn == -INFINITY ? 0.f : mn;
+      const float alpha = fexp2(m[g] - ms);
+      m[g] = mn;
+      float ls = l[g] * alpha;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[g][e] *= alpha;
+#pragma unroll
+      for (int i = 0; i < KPG; ++i) {
+        const float p = fexp2(s[i] - ms);
+        ls += p;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[g][e] += p * vf[i][e];
+      }
+      l[g] = ls;
+    }
+#pragma unroll
+    for (int i = 0; i < KPG; ++i) {
+      kk[i] = kn[i];
+      vv[i] = vn[i];
+    }
+  }
+
+  // the reduction over the lane groups, HC query heads per pass through LDS
+#pragma unroll
+  for (int c = 0; c < GP; c += HC) {
+    if (c) __syncthreads();
+#pragma unroll
+    for (int hc = 0; hc < HC; ++hc) {
+      float* dst = &so[hc][grp][sub * 8];
+      *reinterpret_cast<float4*>(dst) = make_float4(o[c + hc][0], o[c + hc][1], o[c + hc][2], o[c + hc][3]);
+      *reinterpret_cast<float4*>(dst + 4) = make_float4(o[c + hc][4], o[c + hc][5], o[c + hc][6], o[c + hc][7]);
+      if (sub == 0) {
+        sm[hc][grp] = m[c + hc];
+        sl[hc][grp] = l[c + hc];
+      }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < HC * D; idx += 256) {
+      const int hc = idx / D, d = idx - hc * D;
+      if (c + hc >= G) continue;
+      float M = -INFINITY;
+      for (int r = 0; r < NG; ++r) M = fmaxf(M, sm[hc][r]);
+      const float Ms = M == -INFINITY ? 0.f : M;
+      float L = 0.f, acc = 0.f;
+      for (int r = 0; r < NG; ++r) {
+        const float w = fexp2(sm[hc][r] - Ms);
+        L += w * sl[hc][r];
+        acc += w * so[hc][r][d];
+      }
+      const size_t base = (((size_t)split * a.B + b) * a.H + (size_t)hk * G + c + hc) * (D + 2);
+      a.ws[base + 2 + d] = acc;
+      if (d == 0) {
+        a.ws[base] = M;
+        a.ws[base + 1] = L;
+      }
+    }
+  }
+}
+
+template <int D>
+__global__ void __launch_bounds__(D) decode_combine_kernel(const float* __restrict__ ws, int splits, int B, int H,
+                                                           bf16* __restrict__ ctx, long long ldo,
+                                                           float* __restrict__ lse) {
+  const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
+  const size_t stride = (size_t)B * H * (D + 2);
+  const float* p = ws + ((size_t)b * H + h) * (D + 2);
+  float M = -INFINITY;
+  for (int s = 0; s < splits; ++s) M = fmaxf(M, p[s * stride]);
+  const float Ms = M == -INFINITY ? 0.f : M;
+  float L = 0.f, acc = 0.f;
+  for (int s = 0; s < splits; ++s) {
+    const float w = fexp2(p[s * stride] - Ms);
+    L += w * p[s * stride + 1];
+    acc += w * p[s * stride + 2 + d];
+  }
+  const bool live = L > 0.f;
+  ctx[(size_t)b * ldo + (size_t)h * D + d] = (bf16)(live ? acc / L : 0.f);
+  if (d == 0) lse[(size_t)b * H + h] = live ? M * kLn2 + logf(L) : -INFINITY;
+}
+
+template <int D>
+void launch_split(int GP, dim3 grid, hipStream_t s, const DecodeArgs& a) {
+  switch (GP) {
+    case 1: hipLaunchKernelGGL((decode_split_kernel<D, 1>), grid, dim3(256), 0, s, a); break;
+    case 2: hipLaunchKernelGGL((decode_split_kernel<D, 2>), grid, dim3(256), 0, s, a); break;
+    case 4: hipLaunchKernelGGL((decode_split_kernel<D, 4>), grid, dim3(256), 0, s, a); break;
+    default: hipLaunchKernelGGL((decode_split_kernel<D, 8>), grid, dim3(256), 0, s, a); break;
+  }
+}
+
+}  // namespace
+
+DTD_EXPORT int dtd_attn_decode_key_tile() { return kKeyTile; }
+
+// ws: fp32 workspace of ws_floats >= splits * B * H * (D + 2) floats.  ldq, ldo: row strides of q and ctx
+// in elements.  splits beyond the number of key tiles are cut to it.
+DTD_EXPORT int dtd_attn_decode(const void* q, long ldq, const void* k, const void* v, const int* kv_len,
+                               const int* kv_start, void* ctx, long ldo, float* lse, float* ws, long ws_floats, int B,
+                               int H, int Hkv, int D, int Smax, int window, float scale, int splits, hipStream_t s) {
+  if (B <= 0 || H <= 0) return 0;
+  if (!q || !k || !v || !kv_len || !ctx || !lse || !ws) return (int)hipErrorInvalidValue;
+  if (Hkv <= 0 || H % Hkv || H / Hkv > kMaxGroup) return (int)hipErrorInvalidValue;
+  if (D != 64 && D != 128) return (int)hipErrorInvalidValue;
+  if (ldq % 8 || ldq < (long)H * D || ldo < (long)H * D) return (int)hipErrorInvalidValue;
+  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16) return (int)hipErrorInvalidValue;
+  if (Smax <= 0 || window < 0 || splits < 1 || B > 65535 || Hkv > 65535) return (int)hipErrorInvalidValue;
+  const int tiles = (Smax + kKeyTile - 1) / kKeyTile;
+  if (splits > tiles) splits = tiles;
+  if (ws_floats < (long)splits * B * H * (D + 2)) return (int)hipErrorInvalidValue;
+  const int G = H / Hkv;
+  DecodeArgs a;
+  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v;
+  a.kv_len = kv_len; a.kv_start = kv_start; a.ws = ws; a.ldq = ldq;
+  a.B = B; a.H = H; a.Hkv = Hkv; a.G = G; a.Smax = Smax; a.window = window;
+  a.kps = kKeyTile * ((tiles + splits - 1) / splits);
+  a.scale2 = scale * kLog2e;
+  const int GP = G <= 1 ? 1 : (G <= 2 ? 2 : (G <= 4 ? 4 : 8));
+  const dim3 grid(splits, Hkv, B);
+  if (D == 64) {
+    launch_split<64>(GP, grid, s, a);
+    hipLaunchKernelGGL((decode_combine_kernel<64>), dim3(H, B), dim3(64), 0, s, ws, splits, B, H, (bf16*)ctx,
+                       (long long)ldo, lse);
+  } else {
+    launch_split<128>(GP, grid, s, a);
+    hipLaunchKernelGGL((decode_combine_kernel<128>), dim3(H, B), dim3(128), 0, s, ws, splits, B, H, (bf16*)ctx,
+                       (long long)ldo, lse);
+  }
+  DTD_LAUNCH_CHECK();
+}
+
+// qkv [B*Sq, (H + 2 Hkv) D] with row stride ld; kc, vc [B, Hkv, Smax, D]; overflow: one int32.
+DTD_EXPORT int dtd_rope_append(int dtype, void* qkv, const float* table, void* kc, void* vc, const int* kv_len,
+                               int* overflow, int B, int Sq, int H, int Hkv, int D, long ld, int Smax, int max_pos,
+                               hipStream_t s) {
+  if (B <= 0 || Sq <= 0 || H <= 0) return 0;
+  if (!qkv || !table || !kc || !vc || !kv_len || !overflow) return (int)hipErrorInvalidValue;
+  if (Hkv <= 0 || H % Hkv) return (int)hipErrorInvalidValue;
+  if (D <= 0 || D % 16 != 0 || ld % 8 != 0 || ld < (long)(H + 2 * Hkv) * D || max_pos <= 0 || Smax <= 0)
+    return (int)hipErrorInvalidValue;
+  if (((uintptr_t)qkv | (uintptr_t)kc | (uintptr_t)vc) % 16) return (int)hipErrorInvalidValue;
+  const size_t items = (size_t)B * Sq * (H + 2 * Hkv) * (D >> 4);
+  size_t blocks = (items + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  if (dtype == kBF16)
+    hipLaunchKernelGGL((rope_append_kernel<bf16>), dim3(blocks), dim3(256), 0, s, (bf16*)qkv, table, (bf16*)kc,
+                       (bf16*)vc, kv_len, overflow, items, Sq, H, Hkv, D, (size_t)ld, Smax, max_pos, 1.f);
+  else
+    hipLaunchKernelGGL((rope_append_kernel<float>), dim3(blocks), dim3(256), 0, s, (float*)qkv, table, (float*)kc,
+                       (float*)vc, kv_len, overflow, items, Sq, H, Hkv, D, (size_t)ld, Smax, max_pos, 1.f);
+  DTD_LAUNCH_CHECK();
+}

@@ -488,6 +488,62 @@ def rope_(qkv: torch.Tensor, table: torch.Tensor, B: int, S: int, H: int, D: int
     return qkv
 
 
+def rope_append_(qkv: torch.Tensor, table: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                 kv_len: torch.Tensor, B: int, Sq: int, H: int, D: int, kv_heads: int | None = None,
+                 overflow: torch.Tensor | None = None) -> torch.Tensor:
+    """``rope_`` with ``pos = kv_len[b] + s`` IN PLACE on the packed ``qkv [B*Sq, (H + 2*Hkv)*D]`` (bitwise
+    the same rotation), plus the KV-cache append: the rotated k row and the v row of token (b, s) go to
+    slot ``kv_len[b] + s`` of ``k_cache`` / ``v_cache [B, Hkv, Smax, D]``.  ``kv_len``: device int32 [B],
+    read on the device and NOT advanced (the caller adds Sq once per step, after the last layer).  A slot
+    outside [0, Smax) is not written and sets ``overflow`` (an int32 tensor of one element) to 1.  Returns qkv."""
+    Hkv = H if kv_heads is None else int(kv_heads)
+    if Hkv <= 0 or H % Hkv:
+        raise ValueError(f"rope_append_: kv_heads = {Hkv} must divide the {H} query heads")
+    width = (H + 2 * Hkv) * D
+    if qkv.dim() != 2 or qkv.shape[0] != B * Sq or qkv.shape[1] != width or qkv.stride(1) != 1:
+        raise ValueError(f"rope_append_: qkv must be [B*Sq, (H + 2*Hkv)*D] = [{B * Sq}, {width}], got {tuple(qkv.shape)}")
+    if tuple(table.shape[1:]) != (D // 2, 2) or table.dtype != torch.float32 or table.device != qkv.device:
+        raise ValueError("rope_append_: table must be rope_table(max_positions, D) (fp32 [P, D/2, 2]) on qkv's device")
+    if k_cache.dim() != 4 or tuple(k_cache.shape[:2]) != (B, Hkv) or k_cache.shape[3] != D \
+            or v_cache.shape != k_cache.shape or k_cache.dtype != qkv.dtype or v_cache.dtype != qkv.dtype \
+            or not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise ValueError(f"rope_append_: k_cache / v_cache must be contiguous [B, Hkv, Smax, D] = [{B}, {Hkv}, Smax, {D}] "
+                         f"of qkv's dtype, got {tuple(k_cache.shape)} / {tuple(v_cache.shape)}")
+    if kv_len.numel() != B:
+        raise ValueError(f"rope_append_: kv_len must hold one length per sequence ({B})")
+    Smax = k_cache.shape[2]
+    if overflow is None:
+        overflow = torch.zeros(1, dtype=torch.int32, device=qkv.device)
+    if _kernel_dtype(qkv) and D % 16 == 0 and qkv.stride(0) % 8 == 0 and qkv.data_ptr() % 16 == 0:
+        if not _lib.has("dtd_rope_append"):
+            raise _lib.KernelError("the kernel library has no KV-cache append entry point (stale build)")
+        table = table.contiguous()
+        kv32 = kv_len.reshape(-1).to(device=qkv.device, dtype=torch.int32).contiguous()
+        _lib.call("dtd_rope_append", _lib.dt(qkv), qkv.data_ptr(), table.data_ptr(), k_cache.data_ptr(),
+                  v_cache.data_ptr(), kv32.data_ptr(), overflow.data_ptr(), B, Sq, H, Hkv, D, qkv.stride(0), Smax,
+                  table.shape[0], _lib.stream())
+        return qkv
+    slot = kv_len.reshape(B, 1).to(device=qkv.device, dtype=torch.int64) + torch.arange(Sq, device=qkv.device)
+    rope_(qkv, table, B, Sq, H, D, pos=slot, kv_heads=Hkv)
+    fits = (slot >= 0) & (slot < Smax)
+    overflow.copy_(torch.maximum(overflow, (~fits).any().to(overflow.dtype).reshape(overflow.shape)))
+    # index_copy_ with the slots clamped into the cache.  A row that does not fit lands on slot 0 or
+    # Smax - 1 and carries what that slot ends up holding anyway -- the row that does belong there, if the
+    # step has one, else the slot's old content -- so duplicate indices all write the same value.
+    clamped = slot.clamp(0, Smax - 1)                                                   # [B, Sq]
+    writer = clamped - (slot - torch.arange(Sq, device=qkv.device))                     # the s that owns the slot
+    has = ((writer >= 0) & (writer < Sq)).view(B, 1, Sq, 1)
+    rows = (torch.arange(B, device=qkv.device).view(B, 1, 1) * Hkv
+            + torch.arange(Hkv, device=qkv.device).view(1, Hkv, 1)) * Smax + clamped.view(B, 1, Sq)
+    x = qkv.view(B, Sq, H + 2 * Hkv, D)
+    pick = writer.clamp(0, Sq - 1).view(B, 1, Sq, 1).expand(B, Hkv, Sq, D)
+    for cache, new in ((k_cache, x[:, :, H:H + Hkv]), (v_cache, x[:, :, H + Hkv:])):
+        flat = cache.view(B * Hkv * Smax, D)
+        val = torch.where(has, new.transpose(1, 2).gather(2, pick), flat[rows.reshape(-1)].view(B, Hkv, Sq, D))
+        flat.index_copy_(0, rows.reshape(-1), val.reshape(-1, D))
+    return qkv
+
+
 def _swiglu_kernel(t: torch.Tensor, f: int) -> bool:
     return _kernel_dtype(t) and f % 8 == 0 and _lib.has("dtd_swiglu_fwd")
 
