@@ -836,6 +836,15 @@ __global__ void __launch_bounds__(256, OCC) attn_bwd_dkdv_win_kernel(BwdArgs a) 
   constexpr bool DROP = false, ALIBI = false, MASK = true, RANGE = MODE == 1, DOC = MODE == 2, GQA = true, WIN = true;
 #include "attention_bwd_dkdv_body.h"
 }
+// The unmasked D = 64, 128-row-tile, 2-waves-per-SIMD form with the Q / dO tiles delivered by LDS-DMA
+// and (PIPE) the S / dP MFMAs issued one query sub-block ahead, into a second accumulator pair held by
+// the registers the DMA frees (attention_bwd_dkdv_pipe_body.h).  A kernel of its own name, so that the
+// instantiations above keep their symbols and their code; same arithmetic, bit-equal results.
+template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
+template <bool DROP, bool PIPE>
+__global__ void __launch_bounds__(256, 2) attn_bwd_dkdv_pipe_kernel(BwdArgs a) {
+#include "attention_bwd_dkdv_pipe_body.h"
+}
 
 // dQ: grid (ceil(S/128), B*H); block 256 = 4 waves x 32 queries (query on the lane, as in the
 // forward); recomputes S^T and dP^T per 64-key tile and accumulates dQ^T = K^T.dS^T in
@@ -1466,6 +1475,16 @@ static int bwd_form() {
   }
   return g_bwd_form;
 }
+// dK/dV form of the unmasked D = 64 call (not causal, no ALiBi, S % 128 == 0) at 128-row tiles and 2
+// waves per SIMD: 0 = attn_bwd_dkdv_kernel (register-staged tiles), 1 = attn_bwd_dkdv_pipe_kernel with
+// LDS-DMA tiles only, 2 = with the score MFMAs one sub-block ahead as well.  Read at every launch, so
+// that scripts/bench_attn.py --dkdv-arms can alternate the arms in one process.
+// DTD_ATTN_DKDV=old / dma / pipe.
+constexpr int kDkdvFormDefault = 2;
+static int dkdv_form() {
+  const char* e = getenv("DTD_ATTN_DKDV");
+  return !e ? kDkdvFormDefault : strcmp(e, "old") == 0 ? 0 : strcmp(e, "dma") == 0 ? 1 : strcmp(e, "pipe") == 0 ? 2 : kDkdvFormDefault;
+}
 static bool bwd_fused() { return bwd_form() != 0; }
 static bool bwd_fused8() { return bwd_form() == 1; }
 
@@ -1760,6 +1779,12 @@ static void launch_bwd_plain(dim3 grid, bool run_dq, bool run_dkdv, hipStream_t 
     // query row at 2 blocks per CU (75 KB LDS each); DTD_ATTN_DKDV_BM=64 selects the old tile
     const int bm = getenv("DTD_ATTN_DKDV_BM") ? atoi(getenv("DTD_ATTN_DKDV_BM")) : 128;
     if (!run_dkdv) {}
+    else if (bm == 128 && occupancy(1) != 1 && !a.causal && !a.slopes && a.S % 128 == 0 && dkdv_form() != 0) {
+      with_const<2>(a.maskB != nullptr, [&](auto drop) { with_const<2>(dkdv_form() == 2, [&](auto pipe) {
+        constexpr bool DROP = decltype(drop)::value, PIPE = decltype(pipe)::value;
+        hipLaunchKernelGGL((attn_bwd_dkdv_pipe_kernel<DROP, PIPE>), grid, dim3(256), 0, s, a);
+      }); });
+    }
     else if (bm == 128 && occupancy(1) == 1) launch_dkdv<64, 1, 128>(grid, s, a);
     else if (bm == 128) launch_dkdv<64, 2, 128>(grid, s, a);
     else if (occupancy(1) >= 2) launch_dkdv<64, 2, 64>(grid, s, a);

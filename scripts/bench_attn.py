@@ -17,7 +17,12 @@ interleaved, ``--rounds`` times over; each figure is the median of its rounds (t
 
 ``--docs N [N ...]``: the document-mask (sequence packing) kernels -- every row holds N equal
 documents (S // N tokens each, the last takes the remainder).  Same records, with ``"docs": N``;
-interleaved with the call without a range like ``--valid-frac`` (both flags may be given)."""
+interleaved with the call without a range like ``--valid-frac`` (both flags may be given).
+
+``--dkdv-arms``: the three dK/dV kernels of the unmasked call (DTD_ATTN_DKDV=old / dma / pipe: register-
+staged tiles, LDS-DMA tiles, LDS-DMA tiles with the score MFMAs one sub-block ahead) at S = 512, H = 12,
+p = P, B = 256 and 1024 (``--dkdv-batches``).  Same protocol: the arms alternate inside every round,
+medians over ``--rounds``, one JSON line per (B, arm) with dkdv_us (the kernel alone) and bwd_us."""
 import argparse
 import json
 import os
@@ -105,8 +110,53 @@ def ranged(args, B, S, H, D, p, causal, qkv, dctx, rng, slopes=None):
                 fh.write(line + "\n")
 
 
+DKDV_ARMS = ("old", "dma", "pipe")
+
+
+def dkdv_arms(args, S, H, D, p):
+    """dK/dV alone and the whole backward per arm of DTD_ATTN_DKDV (read at every launch), the arms
+    interleaved over rounds, at B * H = 3072 and 12288.  One JSON line per (B, arm)."""
+    for B in args.dkdv_batches:
+        qkv = torch.randn(B * S, 3 * H * D, device="cuda").to(torch.bfloat16)
+        dctx = torch.randn(B * S, H * D, device="cuda").to(torch.bfloat16)
+        rng = RngState(1, device="cuda")
+        for _ in range(20):   # clock / cache warm-up
+            A.attn_fwd(qkv, B, S, H, D, False, None, p, rng, 3)
+        ctx, lse, mk = A.attn_fwd(qkv, B, S, H, D, False, None, p, rng, 3)
+        torch.cuda.synchronize()
+        bwd = lambda: A.attn_bwd(dctx, qkv, ctx, lse, B, S, H, D, False, None, p, rng, 3, mk)  # noqa: E731
+        times = {arm: {"dkdv_us": [], "bwd_us": []} for arm in DKDV_ARMS}
+        try:
+            for _ in range(args.rounds):
+                for arm in DKDV_ARMS:
+                    os.environ["DTD_ATTN_DKDV"] = arm
+                    times[arm]["bwd_us"].append(timeit(bwd))
+                    try:     # (dK/dV alone reads an unwritten delta: wrong values, same work)
+                        A.set_bwd_kernels(dq=False, dkdv=True)
+                        times[arm]["dkdv_us"].append(timeit(bwd))
+                    finally:
+                        A.set_bwd_kernels(True, True)
+        finally:
+            os.environ.pop("DTD_ATTN_DKDV", None)
+        for arm in DKDV_ARMS:
+            rec = {"tag": args.tag, "dkdv_arm": arm, "B": B, "S": S, "H": H, "D": D, "p": p, "rounds": args.rounds}
+            for k, v in times[arm].items():
+                rec[k] = round(statistics.median(v), 1)
+                rec[k + "_minmax"] = [round(min(v), 1), round(max(v), 1)]
+            line = json.dumps(rec)
+            print(line, flush=True)
+            if args.out:
+                with open(args.out, "a") as fh:
+                    fh.write(line + "\n")
+        del qkv, dctx, ctx, lse, mk
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--dkdv-arms", action="store_true",
+                    help="time the dK/dV arms old / dma / pipe (DTD_ATTN_DKDV) interleaved, S = 512, H = 12, D = 64")
+    ap.add_argument("--dkdv-batches", type=int, nargs="+", default=[256, 1024],
+                    help="--dkdv-arms: batch sizes (B * 12 heads = 3072 and 12288 by default)")
     ap.add_argument("occ", nargs="*", help='occupancy variants "fwd,dkdv,dq", "fused" or "fused:<occ>"')
     ap.add_argument("--valid-frac", type=float, nargs="+", default=None,
                     help="time the key-range kernels at these valid fractions of S (right-padded rows)")
@@ -119,6 +169,9 @@ def main():
     B, S, H, D = int(os.environ.get("B", 32)), int(os.environ.get("S", 512)), int(os.environ.get("H", 12)), 64
     p = float(os.environ.get("P", 0.1))
     causal = os.environ.get("CAUSAL", "0") == "1"
+    if args.dkdv_arms:
+        dkdv_arms(args, 512, 12, D, p)
+        return
     qkv = torch.randn(B * S, 3 * H * D, device="cuda").to(torch.bfloat16)
     dctx = torch.randn(B * S, H * D, device="cuda").to(torch.bfloat16)
     rng = RngState(1, device="cuda")
