@@ -224,53 +224,99 @@ def _linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     return G.linear_any(x, w) if x.is_cuda else F.linear(x, w)
 
 
+def fused_attn_half_fwd(ctx, x, layer, key_range, doc_range, position_ids, table, qkv_w, o_w, g1, g2):
+    """The attention half of the fused forward, apart from the FFN so that a layer with another FFN on the same
+    attention half (the mixture-of-experts layer of models/moe.py, which has no fused path yet) can share it:
+    x [B, S, h] -> (z1, f_in) with z1 = x + attention(RMS1(x)) and f_in = RMS2(z1), both [T, h], and the tensors
+    its backward reads, which the caller saves in this order in front of its own.  The non-tensor state goes onto
+    ``ctx``."""
+    c, rt = layer.cfg, layer.rt
+    B, S, h = x.shape
+    H, D = c.num_heads, c.head_dim
+    Hkv = c.kv_heads if c.kv_heads != H else None      # None: the multi-head kernels and layout
+    T = B * S
+    p_a = c.attn_dropout if layer.training else 0.0
+    rng = rt.rng
+    sa = rng.sid(layer.sid_attn)
+    x2d = x.reshape(T, h)
+    eps = c.ln_eps
+    _, a_in, r1 = Fx.rms_fwd(None, x2d, g1, eps)
+    qkv = _linear(a_in, qkv_w)
+    Fx.rope_(qkv, table, B, S, H, D, pos=position_ids, kv_heads=Hkv)   # in place: the rotated qkv is what is kept
+    actx, lse, amask = A.attn_fwd(qkv, B, S, H, D, c.causal, None, p_a, rng, sa,
+                                  key_range=key_range, doc_range=doc_range, kv_heads=Hkv,
+                                  window=c.sliding_window or None)
+    o = _linear(actx, o_w)
+    z1, f_in, r2 = Fx.rms_fwd(o, x2d, g2, eps)             # z1 = x + o and RMS2(z1) in one pass
+    ctx.layer = layer
+    ctx.amask = amask
+    ctx.key_range, ctx.doc_range, ctx.position_ids, ctx.table = key_range, doc_range, position_ids, table
+    ctx.rng = rng
+    ctx.meta = (B, S, h, H, D, p_a, sa)
+    ctx.kv_heads = Hkv
+    return z1, f_in, (x2d, a_in, qkv, actx, lse, z1, f_in, r1, r2)
+
+
+ATTN_HALF_SAVED = 9     # tensors fused_attn_half_fwd hands back for save_for_backward
+
+
+def fused_bwd_begin(ctx, dout):
+    """Start of a fused layer's backward: the step's batched weight transposes (first layer backward only) and
+    dout as contiguous [T, h] rows."""
+    layer = ctx.layer
+    B, S, h = ctx.meta[:3]
+    pend, layer.rt.pending_wt = layer.rt.pending_wt, None
+    if pend:   # first layer backward of the step: every layer's W^T in one launch
+        G.prepare_transposes(pend)
+    return dout.reshape(B * S, h).contiguous()
+
+
+def fused_attn_half_bwd(ctx, saved, dfin, dout, qkv_w, o_w, g1, g2):
+    """The attention half of the fused backward: from dfin (f_in's gradient) and dout (z1 is also out's
+    residual) down to dx [B, S, h]; ``saved`` as ``fused_attn_half_fwd`` returned it."""
+    c, rng = ctx.layer.cfg, ctx.rng
+    B, S, h, H, D, p_a, sa = ctx.meta
+    x2d, a_in, qkv, actx, lse, z1, f_in, r1, r2 = saved
+    # f_in = RMS2(z1) and z1 is also out's residual: dz1 = RMS2'(dfin) + dout; z1 = x + o, so dz1
+    # is both o's gradient and the residual term of dx
+    dz1 = Fx.rms_bwd(dfin, dout, z1, r2, g2, dgamma=grad_dst(g2))
+    grad_done(g2)
+    emit_wgrad(o_w, dz1, actx, async_ok=True)
+    dctx = _dgrad(dz1, o_w)
+    dqkv = A.attn_bwd(dctx, qkv, actx, lse, B, S, H, D, c.causal, None, p_a, rng, sa, ctx.amask,
+                      key_range=ctx.key_range, doc_range=ctx.doc_range, kv_heads=ctx.kv_heads,
+                      window=c.sliding_window or None)
+    # the rotation's adjoint is its inverse: dqkv back in front of the rotary embedding
+    Fx.rope_(dqkv, ctx.table, B, S, H, D, pos=ctx.position_ids, inverse=True, kv_heads=ctx.kv_heads)
+    emit_wgrad(qkv_w, dqkv, a_in, async_ok=True)
+    dain = _dgrad(dqkv, qkv_w)
+    dx = Fx.rms_bwd(dain, dz1, x2d, r1, g1, dgamma=grad_dst(g1))
+    grad_done(g1)
+    return dx.view(B, S, h)
+
+
 class _FusedLlamaLayerFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, layer: LlamaLayer, key_range, doc_range, position_ids, table, *params):
-        c, rt = layer.cfg, layer.rt
+        rt = layer.rt
         (qkv_w, o_w, g1, gu_w, down_w, g2) = params
         B, S, h = x.shape
-        H, D = c.num_heads, c.head_dim
-        Hkv = c.kv_heads if c.kv_heads != H else None      # None: the multi-head kernels and layout
-        T = B * S
-        p_a = c.attn_dropout if layer.training else 0.0
-        rng = rt.rng
-        sa = rng.sid(layer.sid_attn)
-        x2d = x.reshape(T, h)
-        eps = c.ln_eps
-        _, a_in, r1 = Fx.rms_fwd(None, x2d, g1, eps)
-        qkv = _linear(a_in, qkv_w)
-        Fx.rope_(qkv, table, B, S, H, D, pos=position_ids, kv_heads=Hkv)   # in place: the rotated qkv is what is kept
-        actx, lse, amask = A.attn_fwd(qkv, B, S, H, D, c.causal, None, p_a, rng, sa,
-                                      key_range=key_range, doc_range=doc_range, kv_heads=Hkv,
-                                      window=c.sliding_window or None)
-        o = _linear(actx, o_w)
-        z1, f_in, r2 = Fx.rms_fwd(o, x2d, g2, eps)             # z1 = x + o and RMS2(z1) in one pass
+        z1, f_in, attn_saved = fused_attn_half_fwd(ctx, x, layer, key_range, doc_range, position_ids, table,
+                                                   qkv_w, o_w, g1, g2)
         gu = _linear(f_in, gu_w)
         a = Fx.swiglu_fwd(gu)
         y = _linear(a, down_w)
-        out = Fx.dropout_add(y, z1, 0.0, rng, 0)
-        ctx.save_for_backward(x2d, a_in, qkv, actx, lse, z1, f_in, gu, r1, r2, a if rt.keep_ffn_act else None)
-        ctx.layer = layer
-        ctx.amask = amask
-        ctx.key_range, ctx.doc_range, ctx.position_ids, ctx.table = key_range, doc_range, position_ids, table
-        ctx.rng = rng
-        ctx.meta = (B, S, h, H, D, p_a, sa)
-        ctx.kv_heads = Hkv
+        out = Fx.dropout_add(y, z1, 0.0, ctx.rng, 0)
+        ctx.save_for_backward(*attn_saved, gu, a if rt.keep_ffn_act else None)
         return out.view(B, S, h)
 
     @staticmethod
     def backward(ctx, dout):
-        layer = ctx.layer
-        c, rng = layer.cfg, ctx.rng
-        B, S, h, H, D, p_a, sa = ctx.meta
-        T = B * S
-        (qkv_w, o_w, g1, gu_w, down_w, g2) = layer.params()
-        pend, layer.rt.pending_wt = layer.rt.pending_wt, None
-        if pend:   # first layer backward of the step: every layer's W^T in one launch
-            G.prepare_transposes(pend)
-        dout = dout.reshape(T, h).contiguous()
-        x2d, a_in, qkv, actx, lse, z1, f_in, gu, r1, r2, a = ctx.saved_tensors
+        (qkv_w, o_w, g1, gu_w, down_w, g2) = ctx.layer.params()
+        dout = fused_bwd_begin(ctx, dout)
+        saved = ctx.saved_tensors
+        attn_saved, (gu, a) = saved[:ATTN_HALF_SAVED], saved[ATTN_HALF_SAVED:]
+        f_in = attn_saved[6]
         # out = z1 + a down_w^T
         da = _dgrad(dout, down_w)
         if a is None:    # a = silu(gate) * up rewritten inside the SwiGLU backward pass
@@ -282,22 +328,8 @@ class _FusedLlamaLayerFn(torch.autograd.Function):
         del a
         emit_wgrad(gu_w, dgu, f_in, async_ok=True)
         dfin = _dgrad(dgu, gu_w)
-        # f_in = RMS2(z1) and z1 is also out's residual: dz1 = RMS2'(dfin) + dout; z1 = x + o, so dz1
-        # is both o's gradient and the residual term of dx
-        dz1 = Fx.rms_bwd(dfin, dout, z1, r2, g2, dgamma=grad_dst(g2))
-        grad_done(g2)
-        emit_wgrad(o_w, dz1, actx, async_ok=True)
-        dctx = _dgrad(dz1, o_w)
-        dqkv = A.attn_bwd(dctx, qkv, actx, lse, B, S, H, D, c.causal, None, p_a, rng, sa, ctx.amask,
-                          key_range=ctx.key_range, doc_range=ctx.doc_range, kv_heads=ctx.kv_heads,
-                          window=c.sliding_window or None)
-        # the rotation's adjoint is its inverse: dqkv back in front of the rotary embedding
-        Fx.rope_(dqkv, ctx.table, B, S, H, D, pos=ctx.position_ids, inverse=True, kv_heads=ctx.kv_heads)
-        emit_wgrad(qkv_w, dqkv, a_in, async_ok=True)
-        dain = _dgrad(dqkv, qkv_w)
-        dx = Fx.rms_bwd(dain, dz1, x2d, r1, g1, dgamma=grad_dst(g1))
-        grad_done(g1)
-        return (dx.view(B, S, h), None, None, None, None, None) + (None,) * 6
+        dx = fused_attn_half_bwd(ctx, attn_saved, dfin, dout, qkv_w, o_w, g1, g2)
+        return (dx, None, None, None, None, None) + (None,) * 6
 
 
 # ---------------------------------------------------------------------------------- HF weight conversion
