@@ -196,8 +196,17 @@ def lm_head_transient_bytes(tokens: int, vocab: int, fused: bool = False, chunks
     return max((r1 - r0) * (v1 - v0) for r0, r1, v0, v1 in head_xent_plan(tokens, vocab, 0, chunks)) * dtype_bytes
 
 
-def kv_cache_bytes(cfg, batch: int, max_len: int, dtype=torch.bfloat16) -> int:
+def kv_cache_bytes(cfg, batch: int, max_len: int, dtype=torch.bfloat16, kv_dtype=None) -> int:
     """Bytes of the K and V tensors of ``ops.kv_cache.KVCache``: 2 L B Hkv Smax D elements (the position
     counters and the decode workspace are not cache-sized and are left out).  Llama-3-8B in bf16 at B = 8,
-    Smax = 8192: 2 x 32 x 8 x 8 x 8192 x 128 x 2 = 8.6 GB; Llama-2-7B (Hkv = 32) four times that."""
-    return 2 * cfg.num_layers * batch * cfg.kv_heads * max_len * cfg.head_dim * torch.empty((), dtype=dtype).element_size()
+    Smax = 8192: 2 x 32 x 8 x 8 x 8192 x 128 x 2 = 8.6 GB; Llama-2-7B (Hkv = 32) four times that.
+
+    ``kv_dtype``: None or ``dtype`` -- the cache in the model's dtype; ``torch.float8_e4m3fn`` or ``"fp8"`` -- the
+    FP8 cache: one byte per element plus one fp32 scale per D-element row, 2 L B Hkv Smax (D + 4) bytes; the
+    Llama-3-8B example: 2 x 32 x 8 x 8 x 8192 x 132 = 4.4 GB."""
+    rows = 2 * cfg.num_layers * batch * cfg.kv_heads * max_len
+    if kv_dtype is not None and kv_dtype != dtype:
+        if kv_dtype != torch.float8_e4m3fn and kv_dtype != "fp8":
+            raise ValueError(f"kv_dtype must be None, dtype, torch.float8_e4m3fn or 'fp8', got {kv_dtype!r}")
+        return rows * (cfg.head_dim + 4)
+    return rows * cfg.head_dim * torch.empty((), dtype=dtype).element_size()

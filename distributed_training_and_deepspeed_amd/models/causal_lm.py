@@ -203,7 +203,7 @@ class CausalLM(nn.Module):
     def generate(self, input_ids: torch.Tensor, max_new_tokens: int, attention_mask: torch.Tensor | None = None,
                  do_sample: bool = False, temperature: float = 1.0, top_k: int = 0, eos_token_id: int | None = None,
                  seed: int = 0, max_len: int | None = None, graph: bool = False,
-                 logits_out: list | None = None) -> torch.Tensor:
+                 logits_out: list | None = None, kv_dtype=None, cache_out: list | None = None) -> torch.Tensor:
         """``input_ids [B, S0]`` continued by ``max_new_tokens`` = N tokens: int64 ``[B, S0 + N]``.  Greedy by
         default; ``do_sample``: temperature, then top-k (0 = the whole vocabulary), drawn with a
         ``torch.Generator`` seeded with ``seed``.  ``attention_mask``: a LEFT-padded batch (``prefill``).  After
@@ -213,7 +213,12 @@ class CausalLM(nn.Module):
 
         ``graph=True`` (GPU): after two eager steps ``decode_step`` is captured once into a HIP graph -- one
         stream, the token a static input -- and replayed; the token selection stays outside the graph.
-        ``logits_out``: a list that receives each step's ``[B, V]`` logits (tests)."""
+        ``logits_out``: a list that receives each step's ``[B, V]`` logits (tests).
+
+        ``kv_dtype``: ``"fp8"`` (or ``torch.float8_e4m3fn``) keeps the cache as e4m3fn codes with one fp32 scale per
+        row (``KVCache.allocate``): half the bytes and half the decode kernel's traffic, at the quantisation's
+        error -- a greedy token may differ from the unquantised cache's.  None: the cache in the model's dtype.
+        ``cache_out``: a list that receives the call's ``KVCache`` (tests)."""
         self._check_generation()
         B, S0 = input_ids.shape
         N = int(max_new_tokens)
@@ -227,7 +232,9 @@ class CausalLM(nn.Module):
         input_ids = input_ids.to(dev)
         if attention_mask is not None:
             attention_mask = attention_mask.to(dev)
-        cache = KVCache.allocate(self.cfg, B, max_len, dev, w.dtype)
+        cache = KVCache.allocate(self.cfg, B, max_len, dev, w.dtype, kv_dtype=kv_dtype)
+        if cache_out is not None:
+            cache_out.append(cache)
         gen = torch.Generator(device=dev).manual_seed(seed) if do_sample else None
         graph = bool(graph) and dev.type == "cuda"
         was_training = self.training

@@ -134,7 +134,12 @@ class LlamaLayer(nn.Module):
         attention being the training forward's over the prompt itself (``key_range`` for a left-padded
         one).  Otherwise one token per sequence (Sq = 1) against the cache (``A.attn_decode``).  The fused
         path runs the kernels of the training forward around it; the reference path the same cache in
-        plain PyTorch."""
+        plain PyTorch.
+
+        An FP8 cache (``cache.quantized``): the append quantises each row (``ops.kv_cache.quantize_kv_ref``'s law,
+        by the quantising kernel on the fused path) and the decode attention reads codes and scales.  The prefill
+        appends the prompt's rows the same way, but the prompt's own attention runs on the unquantised qkv: only
+        the decode steps see quantised keys and values."""
         c, rt = self.cfg, self.rt
         B, Sq, h = x.shape
         H, D, Hkv = c.num_heads, c.head_dim, c.kv_heads
@@ -150,16 +155,19 @@ class LlamaLayer(nn.Module):
             qkv = _linear(a_in, self.qkv_w)
         else:
             qkv = F.linear(ref_rms_norm(x2d, self.n1_g, eps), self.qkv_w)
-        Fx.rope_append_(qkv, table, kc, vc, cache.kv_len, B, Sq, H, D, kv_heads=Hkv, overflow=cache.overflow)
-        if prefill:
+        ks, vs = cache.layer_scales(i)      # (None, None) unless the cache is FP8
+        Fx.rope_append_(qkv, table, kc, vc, cache.kv_len, B, Sq, H, D, kv_heads=Hkv, overflow=cache.overflow,
+                        k_scale=ks, v_scale=vs)
+        if prefill:      # (also with an FP8 cache: the prompt attends its own unquantised k / v)
             attn = A.attn_fwd if fused else A.attn_fwd_ref
             actx = attn(qkv, B, Sq, H, D, c.causal, key_range=key_range, kv_heads=Hkv if Hkv != H else None,
                         window=window)[0]
         elif fused:
             actx, _ = A.attn_decode(qkv, kc, vc, cache.kv_next, B, H, D, Hkv, window, cache.kv_start,
-                                    splits=cache.splits, workspace=cache.workspace)
+                                    splits=cache.splits, workspace=cache.workspace, k_scale=ks, v_scale=vs)
         else:
-            actx, _ = A.attn_decode_ref(qkv, kc, vc, cache.kv_next, B, H, D, Hkv, window, cache.kv_start)
+            actx, _ = A.attn_decode_ref(qkv, kc, vc, cache.kv_next, B, H, D, Hkv, window, cache.kv_start,
+                                        k_scale=ks, v_scale=vs)
         if fused:
             o = _linear(actx, self.o_w)
             z1, f_in, _ = Fx.rms_fwd(o, x2d, self.n2_g, eps)

@@ -108,6 +108,9 @@ _SIGS = {
     "dtd_attn_decode_key_tile": (I, []),
     "dtd_attn_decode": (I, [P, L, P, P, P, P, P, L, P, P, L, I, I, I, I, I, I, F, I, P]),
     "dtd_rope_append": (I, [I, P, P, P, P, P, P, I, I, I, I, I, L, I, I, P]),
+    # (the _fp8 forms, e4m3 codes with per-row fp32 scales: k_scale, v_scale behind the caches; bf16 only, no dtype)
+    "dtd_attn_decode_fp8": (I, [P, L, P, P, P, P, P, P, P, L, P, P, L, I, I, I, I, I, I, F, I, P]),
+    "dtd_rope_append_fp8": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, L, I, I, P]),
     # attention_f32.hip
     "dtd_attn_fwd_f32": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, F, P]),
     "dtd_attn_bwd_f32": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, F, P]),

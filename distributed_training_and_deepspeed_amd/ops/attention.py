@@ -698,8 +698,9 @@ def attn_bwd(dctx, qkv, ctx, lse, B, S, H, D, causal=False, slopes=None, p=0.0, 
 # written, counting the new token; first valid slot, 0 unless the prompt was left-padded).  Sequence b
 # attends the slots max(kv_start[b], hi - W) <= j < hi with hi = min(kv_len[b], Smax) -- a kv_len beyond
 # the cache is clamped, not trusted, before the window is applied; an empty range gives ctx = 0,
-# lse = -inf (the empty-row rule above).
-DECODE_KEY_TILE = 64          # keys per tile of the decode kernel: split boundaries are its multiples
+# lse = -inf (the empty-row rule above).  An FP8 cache holds e4m3fn codes in K / V and one fp32 scale per row in
+# ``k_scale`` / ``v_scale [B, Hkv, Smax]``; its value is float(code) * scale (ops/kv_cache.py).
+DECODE_KEY_TILE = 64         # keys per tile of the decode kernel: split boundaries are its multiples
 _DECODE_MAX_GROUP = 8         # query heads per key/value head the kernel keeps in registers
 _DECODE_WORKGROUPS = 512      # two workgroups for each of the 256 CUs
 
@@ -735,30 +736,51 @@ def _decode_window(window) -> int:
     return int(window)
 
 
-def _check_decode(qkv, k_cache, v_cache, kv_len, B, H, Hkv, D):
+_FP8 = torch.float8_e4m3fn
+
+
+def _check_decode(qkv, k_cache, v_cache, kv_len, B, H, Hkv, D, k_scale=None, v_scale=None) -> bool:
+    """Validates a decode call; returns whether the caches are FP8 (e4m3fn codes with per-row scales)."""
     if qkv.dim() != 2 or tuple(qkv.shape) != (B, (H + 2 * Hkv) * D) or qkv.stride(1) != 1:
         raise ValueError(f"qkv must be [B, (H + 2*Hkv)*D] = [{B}, {(H + 2 * Hkv) * D}], got {tuple(qkv.shape)}")
     if k_cache.dim() != 4 or tuple(k_cache.shape[:2]) != (B, Hkv) or k_cache.shape[3] != D \
             or v_cache.shape != k_cache.shape:
         raise ValueError(f"k_cache / v_cache must be [B, Hkv, Smax, D] = [{B}, {Hkv}, Smax, {D}], got "
                          f"{tuple(k_cache.shape)} / {tuple(v_cache.shape)}")
-    if k_cache.dtype != qkv.dtype or v_cache.dtype != qkv.dtype:
+    fp8 = k_cache.dtype == _FP8 or v_cache.dtype == _FP8
+    if fp8:
+        if k_cache.dtype != v_cache.dtype:
+            raise ValueError("k_cache and v_cache must both be float8_e4m3fn")
+        want = tuple(k_cache.shape[:3])
+        for name, sc in (("k_scale", k_scale), ("v_scale", v_scale)):
+            if sc is None or tuple(sc.shape) != want or sc.dtype != torch.float32 or sc.device != k_cache.device:
+                raise ValueError(f"an FP8 cache needs {name}: fp32 [B, Hkv, Smax] = {list(want)} on the cache's device, got "
+                                 f"{None if sc is None else (tuple(sc.shape), sc.dtype)}")
+    elif k_scale is not None or v_scale is not None:
+        raise ValueError("k_scale / v_scale go with an FP8 (float8_e4m3fn) cache only")
+    elif k_cache.dtype != qkv.dtype or v_cache.dtype != qkv.dtype:
         raise ValueError("the cache must have the activations' dtype")
     if kv_len.numel() != B:
         raise ValueError(f"kv_len must hold one length per sequence ({B}), got {tuple(kv_len.shape)}")
+    return fp8
 
 
-def attn_decode_ref(qkv, k_cache, v_cache, kv_len, B, H, D, kv_heads=None, window=None, kv_start=None, scale=None):
+def attn_decode_ref(qkv, k_cache, v_cache, kv_len, B, H, D, kv_heads=None, window=None, kv_start=None, scale=None,
+                    k_scale=None, v_scale=None):
     """Math reference of ``attn_decode``: plain PyTorch over the whole cache with the slots outside
     [lo, hi) masked, softmax in fp32 (fp64 for fp64 inputs), the rounding points of ``attn_fwd_ref``
-    (ctx rounded once, at the end).  Returns (ctx [B, H*D], lse [B, H] fp32)."""
+    (ctx rounded once, at the end).  An FP8 cache (``k_scale`` / ``v_scale``) is dequantised first --
+    ``float(code) * scale`` in the compute dtype -- and then takes the same math.
+    Returns (ctx [B, H*D], lse [B, H] fp32)."""
     Hkv = _kv_heads(kv_heads, H)
-    _check_decode(qkv, k_cache, v_cache, kv_len, B, H, Hkv, D)
+    fp8 = _check_decode(qkv, k_cache, v_cache, kv_len, B, H, Hkv, D, k_scale, v_scale)
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     Smax = k_cache.shape[2]
     c = _cdt(qkv)
     q = qkv[:, :H * D].reshape(B, H, 1, D).to(c)
     G = H // Hkv
+    if fp8:
+        k_cache, v_cache = k_cache.to(c) * k_scale.to(c).unsqueeze(-1), v_cache.to(c) * v_scale.to(c).unsqueeze(-1)
     k, v = k_cache.to(c).repeat_interleave(G, 1), v_cache.to(c).repeat_interleave(G, 1)     # [B, H, Smax, D]
     s = torch.matmul(q, k.transpose(-1, -2)) * scale                                       # [B, H, 1, Smax]
     lo, hi = _decode_bounds(kv_len.to(qkv.device), kv_start, _decode_window(window), Smax)
@@ -779,32 +801,38 @@ def decode_kernel_supported(qkv: torch.Tensor, H: int, Hkv: int, D: int) -> bool
 
 
 def attn_decode(qkv, k_cache, v_cache, kv_len, B, H, D, kv_heads=None, window=None, kv_start=None, splits=None,
-                workspace: torch.Tensor | None = None, out: tuple | None = None):
+                workspace: torch.Tensor | None = None, out: tuple | None = None, k_scale: torch.Tensor | None = None,
+                v_scale: torch.Tensor | None = None):
     """Attention of one new token per sequence against the cache: ``qkv [B, (H + 2*Hkv)*D]`` is the step's
     packed projection output (only its q block is read; its k / v rows are already in the cache,
     ``functional.rope_append_``), ``k_cache`` / ``v_cache [B, Hkv, Smax, D]``, ``kv_len`` / ``kv_start``
     device int32 [B] as above.  Returns (ctx [B, H*D], lse [B, H] fp32).
 
-    One routing rule: bf16 on the GPU with D 64 / 128 and H / Hkv <= 8 runs the split-KV kernel (a library
-    without it is an error, not a fallback); everything else -- larger groups, fp32, the CPU -- the math
-    reference.  ``splits``: override of ``decode_splits`` (tests, benchmarks).  ``workspace``: fp32 buffer of
+    One routing rule: bf16 on the GPU with D 64 / 128 and H / Hkv <= 8 runs the split-KV kernel -- its FP8
+    sibling when the caches are ``float8_e4m3fn`` codes with their ``k_scale`` / ``v_scale`` (fp32
+    ``[B, Hkv, Smax]``, ops/kv_cache.py) -- and a library without it is an error, not a fallback; everything
+    else -- larger groups, fp32, the CPU -- the math reference.  FP8 caches without scales, or scales of another
+    shape or dtype, are a ``ValueError``.  ``splits``: override of ``decode_splits`` (tests, benchmarks).  ``workspace``: fp32 buffer of
     at least ``decode_workspace_floats`` elements (``KVCache`` holds one, so a captured step allocates
     nothing for it); allocated here when None.  ``out``: (ctx, lse) tensors to write, of the returned
     shapes and dtypes, ctx with unit column stride."""
     Hkv = _kv_heads(kv_heads, H)
     window = _decode_window(window)
-    _check_decode(qkv, k_cache, v_cache, kv_len, B, H, Hkv, D)
+    fp8 = _check_decode(qkv, k_cache, v_cache, kv_len, B, H, Hkv, D, k_scale, v_scale)
     if not decode_kernel_supported(qkv, H, Hkv, D):
-        ctx, lse = attn_decode_ref(qkv, k_cache, v_cache, kv_len, B, H, D, Hkv, window, kv_start)
+        ctx, lse = attn_decode_ref(qkv, k_cache, v_cache, kv_len, B, H, D, Hkv, window, kv_start, k_scale=k_scale,
+                                   v_scale=v_scale)
         if out is not None:
             out[0].copy_(ctx)
             out[1].copy_(lse)
             return out[0], out[1]
         return ctx, lse
-    _require("dtd_attn_decode", "decode")
+    _require("dtd_attn_decode_fp8" if fp8 else "dtd_attn_decode", "FP8 decode" if fp8 else "decode")
     Smax = k_cache.shape[2]
     if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
         raise ValueError("k_cache / v_cache must be contiguous [B, Hkv, Smax, D]")
+    if fp8 and not (k_scale.is_contiguous() and v_scale.is_contiguous()):
+        raise ValueError("k_scale / v_scale must be contiguous [B, Hkv, Smax]")
     tiles = (Smax + DECODE_KEY_TILE - 1) // DECODE_KEY_TILE
     splits = decode_splits(B, Hkv, Smax) if splits is None else int(splits)
     if splits < 1:
@@ -826,6 +854,12 @@ def attn_decode(qkv, k_cache, v_cache, kv_len, B, H, D, kv_heads=None, window=No
         if tuple(ctx.shape) != (B, H * D) or ctx.dtype != qkv.dtype or ctx.stride(1) != 1 or ctx.device != dev \
                 or tuple(lse.shape) != (B, H) or lse.dtype != torch.float32 or not lse.is_contiguous() or lse.device != dev:
             raise ValueError(f"out must be (ctx [{B}, {H * D}] {qkv.dtype}, lse [{B}, {H}] fp32, contiguous) on {dev}")
+    if fp8:
+        _lib.call("dtd_attn_decode_fp8", qkv.data_ptr(), qkv.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
+                  k_scale.data_ptr(), v_scale.data_ptr(), kv_len.data_ptr(), _lib.ptr(kv_start), ctx.data_ptr(),
+                  ctx.stride(0), lse.data_ptr(), workspace.data_ptr(), workspace.numel(), B, H, Hkv, D, Smax, window,
+                  1.0 / math.sqrt(D), splits, _lib.stream())
+        return ctx, lse
     _lib.call("dtd_attn_decode", qkv.data_ptr(), qkv.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
               kv_len.data_ptr(), _lib.ptr(kv_start), ctx.data_ptr(), ctx.stride(0), lse.data_ptr(), workspace.data_ptr(),
               workspace.numel(), B, H, Hkv, D, Smax, window, 1.0 / math.sqrt(D), splits, _lib.stream())

@@ -30,6 +30,9 @@
 //     the model's dtype and lse.
 // Every load address is clamped into [lo, hi), hi <= Smax, so no slot outside the cache -- and no slot
 // that was never written -- is read, whatever kv_len / kv_start hold.  All index arithmetic is 64-bit.
+//
+// dtd_rope_append_fp8 / dtd_attn_decode_fp8: the same two operations on the opt-in FP8 cache (e4m3fn codes
+// and one fp32 scale per row), as sibling kernels further down; the kernels above are not touched by them.
 #include "common.h"
 
 using namespace dtd;
@@ -335,6 +338,353 @@ void launch_split(int GP, dim3 grid, hipStream_t s, const DecodeArgs& a) {
   }
 }
 
+// ---------------------------------------------------------------------------------- the FP8 cache
+// K, V [B, Hkv, Smax, D] of OCP e4m3fn codes, one byte each, and k_scale, v_scale fp32 [B, Hkv, Smax]: one
+// scale per D-element row.  The quantisation law (ops/kv_cache.py, quantize_kv_ref) per row x, x the
+// bf16 values the bf16 cache would hold:
+//     amax = max |x|;   scale = amax / 448 (1 when amax == 0);   code = e4m3(x / scale),
+// both divisions IEEE fp32 (this file is built without fast-math), the conversion the hardware's
+// round-to-nearest-even v_cvt_pk_fp8_f32; the dequantised value is float(code) * scale.
+
+// Max over the LPK (4 or 8) aligned lanes that hold one row; every lane gets it.
+template <int LPK>
+__device__ __forceinline__ float row_max_fp8(float v) {
+  v = fmaxf(v, dpp_f<0xB1>(v));     // quad_perm [1, 0, 3, 2]
+  v = fmaxf(v, dpp_f<0x4E>(v));     // quad_perm [2, 3, 0, 1]
+  if constexpr (LPK == 8) v = fmaxf(v, dpp_f<0x141>(v));   // row_half_mirror: the other quad of the 8
+  return v;
+}
+
+template <int LPK>
+__device__ __forceinline__ float row_sum_fp8(float v) {
+  v += dpp_f<0xB1>(v);
+  v += dpp_f<0x4E>(v);
+  if constexpr (LPK == 8) v += dpp_f<0x141>(v);
+  return v;
+}
+
+// e4m3 codes of 8 floats: two dwords, element e in byte e
+__device__ __forceinline__ uint2 pack_fp8x8(const float (&x)[8]) {
+  uint2 w;
+  int lo = __builtin_amdgcn_cvt_pk_fp8_f32(x[0], x[1], 0, false);
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(x[2], x[3], lo, true);
+  int hi = __builtin_amdgcn_cvt_pk_fp8_f32(x[4], x[5], 0, false);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(x[6], x[7], hi, true);
+  w.x = (unsigned)lo;
+  w.y = (unsigned)hi;
+  return w;
+}
+
+// dtd_rope_append_fp8: rope_append_kernel<bf16>'s rotation, bit for bit, and the quantising append.  One
+// thread holds the 8 + 8 elements at v * 8 and D / 2 + v * 8 of a head row, so a row is spread over the
+// LPK = D / 16 consecutive, LPK-aligned lanes of a wave (the grid stride is a multiple of 256 and the item
+// count one of LPK).  The loop bound is uniform over the workgroup and nothing leaves the body early:
+// every lane, live or not, reaches the row reduction.
+template <int D>
+__global__ void __launch_bounds__(256) rope_append_fp8_kernel(bf16* __restrict__ qkv, const float* __restrict__ table,
+                                                              uint8_t* __restrict__ kc, uint8_t* __restrict__ vc,
+                                                              float* __restrict__ ks, float* __restrict__ vs,
+                                                              const int* __restrict__ kv_len,
+                                                              int* __restrict__ overflow, size_t items, int Sq, int H,
+                                                              int Hkv, size_t ld, int Smax, int max_pos) {
+  constexpr int LPK = D / 16;
+  constexpr int half = D / 2;
+  const int heads = H + 2 * Hkv;
+  for (size_t i0 = blockIdx.x * (size_t)blockDim.x; i0 < items; i0 += (size_t)gridDim.x * blockDim.x) {
+    const bool live = i0 + threadIdx.x < items;
+    const size_t i = live ? i0 + threadIdx.x : items - 1;      // (a dead lane: the last item's indices, no access)
+    const int v = (int)(i % LPK);
+    const size_t hr = i / LPK;
+    const int hd = (int)(hr % heads);
+    const size_t row = hr / heads;
+    const size_t b = row / (size_t)Sq;
+    const long long slot = (long long)kv_len[b] + (long long)(row % (size_t)Sq);
+    const bool fits = slot >= 0 && slot < (long long)Smax;
+    const bool rot = hd < H + Hkv;
+    bf16* x = qkv + row * ld + (size_t)hd * D + v * 8;
+    float oa[8] = {}, ob[8] = {};
+    if (live) {
+      vload<bf16, 8>(x, oa);
+      vload<bf16, 8>(x + half, ob);
+    }
+    if (live && rot) {               // a q or k head: rotate in place (rope_append_kernel's expression)
+      int p = slot < 0 ? 0 : (slot >= (long long)max_pos ? max_pos - 1 : (int)slot);
+      const float* cs = table + ((size_t)p * half + v * 8) * 2;
+      float t[16], ra[8], rb[8];
+      vload<float, 16>(cs, t);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float c = t[2 * j], sn = t[2 * j + 1];
+        ra[j] = __builtin_fmaf(oa[j], c, -(ob[j] * sn));
+        rb[j] = __builtin_fmaf(ob[j], c, oa[j] * sn);
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {  // as rounded to bf16: what the bf16 cache would hold
+        oa[j] = (float)(bf16)ra[j];
+        ob[j] = (float)(bf16)rb[j];
+      }
+      vstore<bf16, 8>(x, oa);
+      vstore<bf16, 8>(x + half, ob);
+    }
+    float amax = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fmaxf(fabsf(oa[j]), fabsf(ob[j])));
+    amax = row_max_fp8<LPK>(amax);   // all 64 lanes are here; a row's lanes share (row, hd)
+    const float scale = amax == 0.f ? 1.f : amax / 448.f;
+    float ca[8], cb[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      ca[j] = oa[j] / scale;
+      cb[j] = ob[j] / scale;
+    }
+    const uint2 wa = pack_fp8x8(ca), wb = pack_fp8x8(cb);
+    if (live && hd >= H) {           // a k or v head
+      if (!fits) {
+        *overflow = 1;
+      } else {
+        const bool isk = hd < H + Hkv;
+        const int hk = isk ? hd - H : hd - H - Hkv;
+        const size_t r = (b * (size_t)Hkv + hk) * (size_t)Smax + (size_t)slot;
+        uint8_t* dst = (isk ? kc : vc) + r * D + v * 8;
+        *reinterpret_cast<uint2*>(dst) = wa;
+        *reinterpret_cast<uint2*>(dst + half) = wb;
+        if (v == 0) (isk ? ks : vs)[r] = scale;
+      }
+    }
+  }
+}
+
+struct DecodeFp8Args {
+  DecodeArgs a;          // a.k / a.v unused (null)
+  const uint8_t* k;      // [B, Hkv, Smax, D] e4m3 codes
+  const uint8_t* v;
+  const float* ks;       // [B, Hkv, Smax]
+  const float* vs;
+};
+
+// 16 codes -> 16 floats (v_cvt_pk_f32_fp8: exact)
+__device__ __forceinline__ void unpack_fp8x16(const uint4 w, float (&f)[16]) {
+  const unsigned d[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)d[i], false);
+    const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)d[i], true);
+    f[4 * i] = lo[0];
+    f[4 * i + 1] = lo[1];
+    f[4 * i + 2] = hi[0];
+    f[4 * i + 3] = hi[1];
+  }
+}
+
+__device__ __forceinline__ float dot16(const bf16x2 (&k)[8], const bf16x2 (&q)[8]) {
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+#if __has_builtin(__builtin_amdgcn_fdot2_f32_bf16)
+    s = __builtin_amdgcn_fdot2_f32_bf16(k[i], q[i], s, false);
+#else
+    s += (float)k[i][0] * (float)q[i][0] + (float)k[i][1] * (float)q[i][1];
+#endif
+  }
+  return s;
+}
+
+// decode_split_kernel on the FP8 cache: the same grid, key tile, clamped addresses, online-softmax state
+// and workspace format (decode_combine_kernel merges its partials).  A lane loads 16 bytes = 16 codes,
+// so a key row takes LPK = D / 16 lanes and a lane holds 16 elements of o per query head.  The codes are
+// exact in bf16: K goes through the same packed-bf16 dot products, and a row's two scales -- loaded by
+// each of its lanes with the row's clamped index -- cost one multiply per key and head each: k_scale[j]
+// on the reduced score, v_scale[j] on the probability before it is accumulated into o.
+template <int D, int GP>
+__global__ void __launch_bounds__(256) decode_split_fp8_kernel(const DecodeFp8Args fa) {
+  constexpr int LPK = D / 16;            // lanes per key row (16 bytes each)
+  constexpr int GPW = 64 / LPK;          // key rows per wave and load instruction
+  constexpr int NG = 4 * GPW;            // lane groups per workgroup
+  constexpr int KPG = kKeyTile / NG;     // keys per lane group and tile
+  constexpr int HC = GP < 2 ? GP : 2;    // query heads per pass of the final reduction (32 KB of LDS)
+  __shared__ __attribute__((aligned(16))) float so[HC][NG][D];
+  __shared__ float sm[HC][NG], sl[HC][NG];
+
+  const DecodeArgs& a = fa.a;
+  const int split = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int sub = lane % LPK;
+  const int grp = wave * GPW + lane / LPK;
+  const int G = a.G;
+
+  int hi = a.kv_len[b];
+  hi = hi < a.Smax ? hi : a.Smax;
+  int lo = a.kv_start ? a.kv_start[b] : 0;
+  lo = lo > 0 ? lo : 0;
+  if (a.window > 0 && hi - a.window > lo) lo = hi - a.window;
+  const int k0 = split * a.kps;
+  const int k1 = k0 + a.kps < hi ? k0 + a.kps : hi;
+  const int lot = lo / kKeyTile * kKeyTile;
+  const int t0 = k0 > lot ? k0 : lot;    // both multiples of the tile
+  if (lo >= hi || t0 >= k1) {            // no key of this split takes part
+    write_empty<D>(a, split, b, hk);
+    return;
+  }
+
+  bf16x2 q[GP][8];
+#pragma unroll
+  for (int g = 0; g < GP; ++g) {
+    bf16x8 x0 = {}, x1 = {};
+    if (g < G) {
+      const bf16* qp = a.q + (size_t)b * a.ldq + ((size_t)hk * G + g) * D + sub * 16;
+      x0 = *reinterpret_cast<const bf16x8*>(qp);
+      x1 = *reinterpret_cast<const bf16x8*>(qp + 8);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      q[g][i][0] = x0[2 * i];
+      q[g][i][1] = x0[2 * i + 1];
+      q[g][4 + i][0] = x1[2 * i];
+      q[g][4 + i][1] = x1[2 * i + 1];
+    }
+  }
+  float m[GP], l[GP], o[GP][16];
+#pragma unroll
+  for (int g = 0; g < GP; ++g) {
+    m[g] = -INFINITY;
+    l[g] = 0.f;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) o[g][e] = 0.f;
+  }
+
+  const size_t rows = ((size_t)b * a.Hkv + hk) * (size_t)a.Smax;    // the head's first row: codes and scales
+  const uint8_t* Kb = fa.k + rows * D + sub * 16;
+  const uint8_t* Vb = fa.v + rows * D + sub * 16;
+  const float* KSb = fa.ks + rows;
+  const float* VSb = fa.vs + rows;
+  const int last = hi - 1;               // lo <= last here: every address stays inside [lo, hi), hi <= Smax
+
+  uint4 kk[KPG], vv[KPG];
+  float ksc[KPG], vsc[KPG];
+#pragma unroll
+  for (int i = 0; i < KPG; ++i) {
+    int j = t0 + i * NG + grp;
+    j = j < last ? j : last;
+    j = j > lo ? j : lo;                 // a masked slot reads a live one: never-written codes and scales may be NaN
+    kk[i] = *reinterpret_cast<const uint4*>(Kb + (size_t)j * D);
+    vv[i] = *reinterpret_cast<const uint4*>(Vb + (size_t)j * D);
+    ksc[i] = KSb[j];
+    vsc[i] = VSb[j];
+  }
+  for (int t = t0; t < k1; t += kKeyTile) {
+    uint4 kn[KPG], vn[KPG];
+    float ksn[KPG], vsn[KPG];
+    const int tn = t + kKeyTile < k1 ? t + kKeyTile : t;     // (the last tile is loaded twice: in bounds)
+#pragma unroll
+    for (int i = 0; i < KPG; ++i) {
+      int j = tn + i * NG + grp;
+      j = j < last ? j : last;
+      j = j > lo ? j : lo;
+      kn[i] = *reinterpret_cast<const uint4*>(Kb + (size_t)j * D);
+      vn[i] = *reinterpret_cast<const uint4*>(Vb + (size_t)j * D);
+      ksn[i] = KSb[j];
+      vsn[i] = VSb[j];
+    }
+    bf16x2 kb[KPG][8];
+    float vf[KPG][16], kq[KPG];
+    bool ok[KPG];
+#pragma unroll
+    for (int i = 0; i < KPG; ++i) {
+      const int j = t + i * NG + grp;
+      ok[i] = j >= lo && j < hi;
+      float kf[16];
+      unpack_fp8x16(kk[i], kf);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        kb[i][e][0] = (bf16)kf[2 * e];
+        kb[i][e][1] = (bf16)kf[2 * e + 1];
+      }
+      unpack_fp8x16(vv[i], vf[i]);
+      kq[i] = ksc[i] * a.scale2;
+    }
+#pragma unroll
+    for (int g = 0; g < GP; ++g) {
+      float s[KPG];
+      float mn = m[g];
+#pragma unroll
+      for (int i = 0; i < KPG; ++i) {
+        const float d = row_sum_fp8<LPK>(dot16(kb[i], q[g])) * kq[i];
+        s[i] = ok[i] ? d : -INFINITY;
+        mn = fmaxf(mn, s[i]);
+      }
+      const float ms = mn == -INFINITY ? 0.f : mn;
+      const float alpha = fexp2(m[g] - ms);
+      m[g] = mn;
+      float ls = l[g] * alpha;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) o[g][e] *= alpha;
+#pragma unroll
+      for (int i = 0; i < KPG; ++i) {
+        const float p = fexp2(s[i] - ms);
+        ls += p;
+        const float pv = p * vsc[i];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) o[g][e] += pv * vf[i][e];
+      }
+      l[g] = ls;
+    }
+#pragma unroll
+    for (int i = 0; i < KPG; ++i) {
+      kk[i] = kn[i];
+      vv[i] = vn[i];
+      ksc[i] = ksn[i];
+      vsc[i] = vsn[i];
+    }
+  }
+
+  // the reduction over the lane groups, HC query heads per pass through LDS
+#pragma unroll
+  for (int c = 0; c < GP; c += HC) {
+    if (c) __syncthreads();
+#pragma unroll
+    for (int hc = 0; hc < HC; ++hc) {
+      float* dst = &so[hc][grp][sub * 16];
+#pragma unroll
+      for (int e = 0; e < 16; e += 4)
+        *reinterpret_cast<float4*>(dst + e) = make_float4(o[c + hc][e], o[c + hc][e + 1], o[c + hc][e + 2], o[c + hc][e + 3]);
+      if (sub == 0) {
+        sm[hc][grp] = m[c + hc];
+        sl[hc][grp] = l[c + hc];
+      }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < HC * D; idx += 256) {
+      const int hc = idx / D, d = idx - hc * D;
+      if (c + hc >= G) continue;
+      float M = -INFINITY;
+      for (int r = 0; r < NG; ++r) M = fmaxf(M, sm[hc][r]);
+      const float Ms = M == -INFINITY ? 0.f : M;
+      float L = 0.f, acc = 0.f;
+      for (int r = 0; r < NG; ++r) {
+        const float w = fexp2(sm[hc][r] - Ms);
+        L += w * sl[hc][r];
+        acc += w * so[hc][r][d];
+      }
+      const size_t base = (((size_t)split * a.B + b) * a.H + (size_t)hk * G + c + hc) * (D + 2);
+      a.ws[base + 2 + d] = acc;
+      if (d == 0) {
+        a.ws[base] = M;
+        a.ws[base + 1] = L;
+      }
+    }
+  }
+}
+
+template <int D>
+void launch_split_fp8(int GP, dim3 grid, hipStream_t s, const DecodeFp8Args& a) {
+  switch (GP) {
+    case 1: hipLaunchKernelGGL((decode_split_fp8_kernel<D, 1>), grid, dim3(256), 0, s, a); break;
+    case 2: hipLaunchKernelGGL((decode_split_fp8_kernel<D, 2>), grid, dim3(256), 0, s, a); break;
+    case 4: hipLaunchKernelGGL((decode_split_fp8_kernel<D, 4>), grid, dim3(256), 0, s, a); break;
+    default: hipLaunchKernelGGL((decode_split_fp8_kernel<D, 8>), grid, dim3(256), 0, s, a); break;
+  }
+}
+
 }  // namespace
 
 DTD_EXPORT int dtd_attn_decode_key_tile() { return kKeyTile; }
@@ -372,6 +722,70 @@ DTD_EXPORT int dtd_attn_decode(const void* q, long ldq, const void* k, const voi
     hipLaunchKernelGGL((decode_combine_kernel<128>), dim3(H, B), dim3(128), 0, s, ws, splits, B, H, (bf16*)ctx,
                        (long long)ldo, lse);
   }
+  DTD_LAUNCH_CHECK();
+}
+
+// dtd_attn_decode on the FP8 cache: k, v [B, Hkv, Smax, D] e4m3 codes, k_scale, v_scale fp32 [B, Hkv, Smax];
+// q / ctx bf16; everything else as dtd_attn_decode (the same workspace, the same combine kernel).
+DTD_EXPORT int dtd_attn_decode_fp8(const void* q, long ldq, const void* k, const void* v, const float* k_scale,
+                                   const float* v_scale, const int* kv_len, const int* kv_start, void* ctx, long ldo,
+                                   float* lse, float* ws, long ws_floats, int B, int H, int Hkv, int D, int Smax,
+                                   int window, float scale, int splits, hipStream_t s) {
+  if (B <= 0 || H <= 0) return 0;
+  if (!q || !k || !v || !k_scale || !v_scale || !kv_len || !ctx || !lse || !ws) return (int)hipErrorInvalidValue;
+  if (Hkv <= 0 || H % Hkv || H / Hkv > kMaxGroup) return (int)hipErrorInvalidValue;
+  if (D != 64 && D != 128) return (int)hipErrorInvalidValue;
+  if (ldq % 8 || ldq < (long)H * D || ldo < (long)H * D) return (int)hipErrorInvalidValue;
+  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 || ((uintptr_t)k_scale | (uintptr_t)v_scale) % 4)
+    return (int)hipErrorInvalidValue;
+  if (Smax <= 0 || window < 0 || splits < 1 || B > 65535 || Hkv > 65535) return (int)hipErrorInvalidValue;
+  const int tiles = (Smax + kKeyTile - 1) / kKeyTile;
+  if (splits > tiles) splits = tiles;
+  if (ws_floats < (long)splits * B * H * (D + 2)) return (int)hipErrorInvalidValue;
+  const int G = H / Hkv;
+  DecodeFp8Args f;
+  DecodeArgs& a = f.a;
+  a.q = (const bf16*)q; a.k = nullptr; a.v = nullptr;
+  a.kv_len = kv_len; a.kv_start = kv_start; a.ws = ws; a.ldq = ldq;
+  a.B = B; a.H = H; a.Hkv = Hkv; a.G = G; a.Smax = Smax; a.window = window;
+  a.kps = kKeyTile * ((tiles + splits - 1) / splits);
+  a.scale2 = scale * kLog2e;
+  f.k = (const uint8_t*)k; f.v = (const uint8_t*)v; f.ks = k_scale; f.vs = v_scale;
+  const int GP = G <= 1 ? 1 : (G <= 2 ? 2 : (G <= 4 ? 4 : 8));
+  const dim3 grid(splits, Hkv, B);
+  if (D == 64) {
+    launch_split_fp8<64>(GP, grid, s, f);
+    hipLaunchKernelGGL((decode_combine_kernel<64>), dim3(H, B), dim3(64), 0, s, ws, splits, B, H, (bf16*)ctx,
+                       (long long)ldo, lse);
+  } else {
+    launch_split_fp8<128>(GP, grid, s, f);
+    hipLaunchKernelGGL((decode_combine_kernel<128>), dim3(H, B), dim3(128), 0, s, ws, splits, B, H, (bf16*)ctx,
+                       (long long)ldo, lse);
+  }
+  DTD_LAUNCH_CHECK();
+}
+
+// dtd_rope_append on the FP8 cache (bf16 qkv, D 64 or 128): kc, vc [B, Hkv, Smax, D] e4m3 codes, ks, vs fp32
+// [B, Hkv, Smax].  A row that does not fit writes neither codes nor a scale and raises the flag.
+DTD_EXPORT int dtd_rope_append_fp8(void* qkv, const float* table, void* kc, void* vc, float* ks, float* vs,
+                                   const int* kv_len, int* overflow, int B, int Sq, int H, int Hkv, int D, long ld,
+                                   int Smax, int max_pos, hipStream_t s) {
+  if (B <= 0 || Sq <= 0 || H <= 0) return 0;
+  if (!qkv || !table || !kc || !vc || !ks || !vs || !kv_len || !overflow) return (int)hipErrorInvalidValue;
+  if (Hkv <= 0 || H % Hkv) return (int)hipErrorInvalidValue;
+  if ((D != 64 && D != 128) || ld % 8 != 0 || ld < (long)(H + 2 * Hkv) * D || max_pos <= 0 || Smax <= 0)
+    return (int)hipErrorInvalidValue;
+  if (((uintptr_t)qkv | (uintptr_t)kc | (uintptr_t)vc) % 16 || ((uintptr_t)ks | (uintptr_t)vs) % 4)
+    return (int)hipErrorInvalidValue;
+  const size_t items = (size_t)B * Sq * (H + 2 * Hkv) * (D >> 4);
+  size_t blocks = (items + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  if (D == 64)
+    hipLaunchKernelGGL((rope_append_fp8_kernel<64>), dim3(blocks), dim3(256), 0, s, (bf16*)qkv, table, (uint8_t*)kc,
+                       (uint8_t*)vc, ks, vs, kv_len, overflow, items, Sq, H, Hkv, (size_t)ld, Smax, max_pos);
+  else
+    hipLaunchKernelGGL((rope_append_fp8_kernel<128>), dim3(blocks), dim3(256), 0, s, (bf16*)qkv, table, (uint8_t*)kc,
+                       (uint8_t*)vc, ks, vs, kv_len, overflow, items, Sq, H, Hkv, (size_t)ld, Smax, max_pos);
   DTD_LAUNCH_CHECK();
 }
 

@@ -490,12 +490,22 @@ def rope_(qkv: torch.Tensor, table: torch.Tensor, B: int, S: int, H: int, D: int
 
 def rope_append_(qkv: torch.Tensor, table: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
                  kv_len: torch.Tensor, B: int, Sq: int, H: int, D: int, kv_heads: int | None = None,
-                 overflow: torch.Tensor | None = None) -> torch.Tensor:
+                 overflow: torch.Tensor | None = None, k_scale: torch.Tensor | None = None,
+                 v_scale: torch.Tensor | None = None) -> torch.Tensor:
     """``rope_`` with ``pos = kv_len[b] + s`` IN PLACE on the packed ``qkv [B*Sq, (H + 2*Hkv)*D]`` (bitwise
     the same rotation), plus the KV-cache append: the rotated k row and the v row of token (b, s) go to
     slot ``kv_len[b] + s`` of ``k_cache`` / ``v_cache [B, Hkv, Smax, D]``.  ``kv_len``: device int32 [B],
     read on the device and NOT advanced (the caller adds Sq once per step, after the last layer).  A slot
-    outside [0, Smax) is not written and sets ``overflow`` (an int32 tensor of one element) to 1.  Returns qkv."""
+    outside [0, Smax) is not written and sets ``overflow`` (an int32 tensor of one element) to 1.  Returns qkv.
+
+    FP8 caches (``torch.float8_e4m3fn``, with ``k_scale`` / ``v_scale`` fp32 ``[B, Hkv, Smax]``): qkv is
+    rotated exactly as above and each row is quantised by ``ops.kv_cache.quantize_kv_ref``'s law -- D codes and
+    one scale per slot, neither written for a row that does not fit.  bf16 on the GPU with D 64 / 128 runs the
+    quantising kernel (same codes and scales, bit for bit); everything else -- the CPU, fp32 activations,
+    another D -- the PyTorch reference."""
+    if k_cache.dtype == torch.float8_e4m3fn or v_cache.dtype == torch.float8_e4m3fn or k_scale is not None \
+            or v_scale is not None:
+        return _rope_append_fp8_(qkv, table, k_cache, v_cache, k_scale, v_scale, kv_len, B, Sq, H, D, kv_heads, overflow)
     Hkv = H if kv_heads is None else int(kv_heads)
     if Hkv <= 0 or H % Hkv:
         raise ValueError(f"rope_append_: kv_heads = {Hkv} must divide the {H} query heads")
@@ -525,22 +535,79 @@ def rope_append_(qkv: torch.Tensor, table: torch.Tensor, k_cache: torch.Tensor, 
         return qkv
     slot = kv_len.reshape(B, 1).to(device=qkv.device, dtype=torch.int64) + torch.arange(Sq, device=qkv.device)
     rope_(qkv, table, B, Sq, H, D, pos=slot, kv_heads=Hkv)
+    x = qkv.view(B, Sq, H + 2 * Hkv, D)
+    _append_rows_ref(slot, overflow, ((k_cache, x[:, :, H:H + Hkv]), (v_cache, x[:, :, H + Hkv:])))
+    return qkv
+
+
+def _append_rows_ref(slot: torch.Tensor, overflow: torch.Tensor, pairs) -> None:
+    """The append of ``rope_append_``'s PyTorch branch: for every (cache ``[B, Hkv, Smax, W]``, new
+    ``[B, Sq, Hkv, W]``) of ``pairs``, row (b, s) of new into slot ``slot[b, s]`` of cache; a slot outside
+    [0, Smax) is not written and raises ``overflow``."""
+    B, Sq = slot.shape
+    dev = slot.device
+    Hkv, Smax = pairs[0][0].shape[1:3]
     fits = (slot >= 0) & (slot < Smax)
     overflow.copy_(torch.maximum(overflow, (~fits).any().to(overflow.dtype).reshape(overflow.shape)))
     # index_copy_ with the slots clamped into the cache.  A row that does not fit lands on slot 0 or
     # Smax - 1 and carries what that slot ends up holding anyway -- the row that does belong there, if the
     # step has one, else the slot's old content -- so duplicate indices all write the same value.
     clamped = slot.clamp(0, Smax - 1)                                                   # [B, Sq]
-    writer = clamped - (slot - torch.arange(Sq, device=qkv.device))                     # the s that owns the slot
+    writer = clamped - (slot - torch.arange(Sq, device=dev))                            # the s that owns the slot
     has = ((writer >= 0) & (writer < Sq)).view(B, 1, Sq, 1)
-    rows = (torch.arange(B, device=qkv.device).view(B, 1, 1) * Hkv
-            + torch.arange(Hkv, device=qkv.device).view(1, Hkv, 1)) * Smax + clamped.view(B, 1, Sq)
+    rows = (torch.arange(B, device=dev).view(B, 1, 1) * Hkv
+            + torch.arange(Hkv, device=dev).view(1, Hkv, 1)) * Smax + clamped.view(B, 1, Sq)
+    for cache, new in pairs:
+        W = cache.shape[3]
+        pick = writer.clamp(0, Sq - 1).view(B, 1, Sq, 1).expand(B, Hkv, Sq, W)
+        flat = cache.view(B * Hkv * Smax, W)
+        val = torch.where(has, new.transpose(1, 2).gather(2, pick), flat[rows.reshape(-1)].view(B, Hkv, Sq, W))
+        flat.index_copy_(0, rows.reshape(-1), val.reshape(-1, W))
+
+
+def _rope_append_fp8_(qkv, table, k_cache, v_cache, k_scale, v_scale, kv_len, B, Sq, H, D, kv_heads, overflow):
+    """``rope_append_`` on FP8 caches (its docstring)."""
+    from .kv_cache import quantize_kv_ref
+    Hkv = H if kv_heads is None else int(kv_heads)
+    if Hkv <= 0 or H % Hkv:
+        raise ValueError(f"rope_append_: kv_heads = {Hkv} must divide the {H} query heads")
+    width = (H + 2 * Hkv) * D
+    if qkv.dim() != 2 or qkv.shape[0] != B * Sq or qkv.shape[1] != width or qkv.stride(1) != 1:
+        raise ValueError(f"rope_append_: qkv must be [B*Sq, (H + 2*Hkv)*D] = [{B * Sq}, {width}], got {tuple(qkv.shape)}")
+    if tuple(table.shape[1:]) != (D // 2, 2) or table.dtype != torch.float32 or table.device != qkv.device:
+        raise ValueError("rope_append_: table must be rope_table(max_positions, D) (fp32 [P, D/2, 2]) on qkv's device")
+    if k_cache.dim() != 4 or tuple(k_cache.shape[:2]) != (B, Hkv) or k_cache.shape[3] != D \
+            or v_cache.shape != k_cache.shape or k_cache.dtype != torch.float8_e4m3fn \
+            or v_cache.dtype != torch.float8_e4m3fn or not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise ValueError(f"rope_append_: FP8 k_cache / v_cache must both be contiguous float8_e4m3fn [B, Hkv, Smax, D] = "
+                         f"[{B}, {Hkv}, Smax, {D}], got {tuple(k_cache.shape)} {k_cache.dtype} / "
+                         f"{tuple(v_cache.shape)} {v_cache.dtype}")
+    Smax = k_cache.shape[2]
+    for name, sc in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if sc is None or tuple(sc.shape) != (B, Hkv, Smax) or sc.dtype != torch.float32 or not sc.is_contiguous() \
+                or sc.device != k_cache.device:
+            raise ValueError(f"rope_append_: an FP8 cache needs {name}, contiguous fp32 [B, Hkv, Smax] = [{B}, {Hkv}, {Smax}]")
+    if kv_len.numel() != B:
+        raise ValueError(f"rope_append_: kv_len must hold one length per sequence ({B})")
+    if overflow is None:
+        overflow = torch.zeros(1, dtype=torch.int32, device=qkv.device)
+    if qkv.is_cuda and qkv.dtype == torch.bfloat16 and D in (64, 128) and qkv.stride(0) % 8 == 0 \
+            and qkv.data_ptr() % 16 == 0:
+        if not _lib.has("dtd_rope_append_fp8"):
+            raise _lib.KernelError("the kernel library has no FP8 KV-cache append entry point (stale build)")
+        table = table.contiguous()
+        kv32 = kv_len.reshape(-1).to(device=qkv.device, dtype=torch.int32).contiguous()
+        _lib.call("dtd_rope_append_fp8", qkv.data_ptr(), table.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                  k_scale.data_ptr(), v_scale.data_ptr(), kv32.data_ptr(), overflow.data_ptr(), B, Sq, H, Hkv, D,
+                  qkv.stride(0), Smax, table.shape[0], _lib.stream())
+        return qkv
+    slot = kv_len.reshape(B, 1).to(device=qkv.device, dtype=torch.int64) + torch.arange(Sq, device=qkv.device)
+    rope_(qkv, table, B, Sq, H, D, pos=slot, kv_heads=Hkv)
     x = qkv.view(B, Sq, H + 2 * Hkv, D)
-    pick = writer.clamp(0, Sq - 1).view(B, 1, Sq, 1).expand(B, Hkv, Sq, D)
-    for cache, new in ((k_cache, x[:, :, H:H + Hkv]), (v_cache, x[:, :, H + Hkv:])):
-        flat = cache.view(B * Hkv * Smax, D)
-        val = torch.where(has, new.transpose(1, 2).gather(2, pick), flat[rows.reshape(-1)].view(B, Hkv, Sq, D))
-        flat.index_copy_(0, rows.reshape(-1), val.reshape(-1, D))
+    kq, ks = quantize_kv_ref(x[:, :, H:H + Hkv])
+    vq, vs = quantize_kv_ref(x[:, :, H + Hkv:])
+    _append_rows_ref(slot, overflow, ((k_cache.view(torch.uint8), kq.view(torch.uint8)), (k_scale.unsqueeze(-1), ks.unsqueeze(-1)),
+                                      (v_cache.view(torch.uint8), vq.view(torch.uint8)), (v_scale.unsqueeze(-1), vs.unsqueeze(-1))))
     return qkv
 
 

@@ -7,9 +7,12 @@ new tokens, over their 112 extra steps: both pay the prefill, the two eager step
 capture once.  The baseline runs ``model(prefix)`` for the same 112 steps (prefix lengths 144 .. 255) and takes
 the argmax of the last position.  Each arm is timed twice, interleaved; the whole 128-token call is reported too.
 
+``--kv-cache-dtype fp8`` runs both ``generate`` arms with the FP8 KV cache (``kv_dtype="fp8"``); the row says so.
+
 One JSON line per (model, B), appended to --out.
 
 Usage: python scripts/bench_generate.py [--out profiles/generate.jsonl] [--models llama-160m,tinyllama-1.1b]
+                                        [--kv-cache-dtype auto|fp8]
 """
 from __future__ import annotations
 
@@ -60,10 +63,12 @@ def main():
     ap.add_argument("--out", type=str, default="")
     ap.add_argument("--models", type=str, default="llama-160m,tinyllama-1.1b")
     ap.add_argument("--batches", type=str, default="1,8")
+    ap.add_argument("--kv-cache-dtype", default="auto", choices=("auto", "fp8"), help="auto: the model's dtype")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_generate.py needs a GPU")
     steps = NEW - SHORT
+    kv_dtype = None if args.kv_cache_dtype == "auto" else args.kv_cache_dtype
     for name in args.models.split(","):
         model = build_model(name, impl="fused", dtype=torch.bfloat16, device="cuda", seed=0).eval()
         for B in (int(b) for b in args.batches.split(",")):
@@ -71,8 +76,8 @@ def main():
             ids = torch.randint(3, model.cfg.vocab_size, (B, PROMPT + NEW), generator=g).cuda()
             prompt = ids[:, :PROMPT]
             arms = {
-                "eager": lambda n: model.generate(prompt, n),
-                "graph": lambda n: model.generate(prompt, n, graph=True),
+                "eager": lambda n: model.generate(prompt, n, kv_dtype=kv_dtype),
+                "graph": lambda n: model.generate(prompt, n, graph=True, kv_dtype=kv_dtype),
             }
             for fn in arms.values():                      # warm-up of every shape the timed calls use
                 fn(SHORT)
@@ -89,7 +94,7 @@ def main():
                 _, t = wall(lambda: recompute(model, ids, PROMPT + SHORT, steps))
                 runs["recompute"].append(t / steps)
             rec = {"case": "generate", "model": model.cfg.name, "B": B, "prompt": PROMPT, "new_tokens": NEW,
-                   "steps_timed": steps, "graph_tokens_equal_eager": same}
+                   "kv_cache_dtype": args.kv_cache_dtype, "steps_timed": steps, "graph_tokens_equal_eager": same}
             for key, r in runs.items():
                 ms = sum(r) / 2 * 1e3
                 rec[f"{key}_ms_per_step"] = round(ms, 4)
