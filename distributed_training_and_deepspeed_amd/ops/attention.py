@@ -808,8 +808,8 @@ def attn_decode(qkv, k_cache, v_cache, kv_len, B, H, D, kv_heads=None, window=No
     ``functional.rope_append_``), ``k_cache`` / ``v_cache [B, Hkv, Smax, D]``, ``kv_len`` / ``kv_start``
     device int32 [B] as above.  Returns (ctx [B, H*D], lse [B, H] fp32).
 
-    One routing rule: bf16 on the GPU with D 64 / 128 and H / Hkv <= 8 runs the split-KV kernel -- its FP8
-    sibling when the caches are ``float8_e4m3fn`` codes with their ``k_scale`` / ``v_scale`` (fp32
+    One routing rule: bf16 on the GPU with D 64 / 128 and H / Hkv <= 8 runs the split-KV kernel -- in its FP8
+    format when the caches are ``float8_e4m3fn`` codes with their ``k_scale`` / ``v_scale`` (fp32
     ``[B, Hkv, Smax]``, ops/kv_cache.py) -- and a library without it is an error, not a fallback; everything
     else -- larger groups, fp32, the CPU -- the math reference.  FP8 caches without scales, or scales of another
     shape or dtype, are a ``ValueError``.  ``splits``: override of ``decode_splits`` (tests, benchmarks).  ``workspace``: fp32 buffer of
@@ -827,7 +827,8 @@ def attn_decode(qkv, k_cache, v_cache, kv_len, B, H, D, kv_heads=None, window=No
             out[1].copy_(lse)
             return out[0], out[1]
         return ctx, lse
-    _require("dtd_attn_decode_fp8" if fp8 else "dtd_attn_decode", "FP8 decode" if fp8 else "decode")
+    entry = "dtd_attn_decode_fp8" if fp8 else "dtd_attn_decode"
+    _require(entry, "FP8 decode" if fp8 else "decode")
     Smax = k_cache.shape[2]
     if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
         raise ValueError("k_cache / v_cache must be contiguous [B, Hkv, Smax, D]")
@@ -854,13 +855,8 @@ def attn_decode(qkv, k_cache, v_cache, kv_len, B, H, D, kv_heads=None, window=No
         if tuple(ctx.shape) != (B, H * D) or ctx.dtype != qkv.dtype or ctx.stride(1) != 1 or ctx.device != dev \
                 or tuple(lse.shape) != (B, H) or lse.dtype != torch.float32 or not lse.is_contiguous() or lse.device != dev:
             raise ValueError(f"out must be (ctx [{B}, {H * D}] {qkv.dtype}, lse [{B}, {H}] fp32, contiguous) on {dev}")
-    if fp8:
-        _lib.call("dtd_attn_decode_fp8", qkv.data_ptr(), qkv.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
-                  k_scale.data_ptr(), v_scale.data_ptr(), kv_len.data_ptr(), _lib.ptr(kv_start), ctx.data_ptr(),
-                  ctx.stride(0), lse.data_ptr(), workspace.data_ptr(), workspace.numel(), B, H, Hkv, D, Smax, window,
-                  1.0 / math.sqrt(D), splits, _lib.stream())
-        return ctx, lse
-    _lib.call("dtd_attn_decode", qkv.data_ptr(), qkv.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
+    scales = (k_scale.data_ptr(), v_scale.data_ptr()) if fp8 else ()
+    _lib.call(entry, qkv.data_ptr(), qkv.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), *scales,
               kv_len.data_ptr(), _lib.ptr(kv_start), ctx.data_ptr(), ctx.stride(0), lse.data_ptr(), workspace.data_ptr(),
               workspace.numel(), B, H, Hkv, D, Smax, window, 1.0 / math.sqrt(D), splits, _lib.stream())
     return ctx, lse

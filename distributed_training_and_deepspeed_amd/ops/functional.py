@@ -503,9 +503,8 @@ def rope_append_(qkv: torch.Tensor, table: torch.Tensor, k_cache: torch.Tensor, 
     one scale per slot, neither written for a row that does not fit.  bf16 on the GPU with D 64 / 128 runs the
     quantising kernel (same codes and scales, bit for bit); everything else -- the CPU, fp32 activations,
     another D -- the PyTorch reference."""
-    if k_cache.dtype == torch.float8_e4m3fn or v_cache.dtype == torch.float8_e4m3fn or k_scale is not None \
-            or v_scale is not None:
-        return _rope_append_fp8_(qkv, table, k_cache, v_cache, k_scale, v_scale, kv_len, B, Sq, H, D, kv_heads, overflow)
+    fp8 = k_cache.dtype == torch.float8_e4m3fn or v_cache.dtype == torch.float8_e4m3fn or k_scale is not None \
+        or v_scale is not None
     Hkv = H if kv_heads is None else int(kv_heads)
     if Hkv <= 0 or H % Hkv:
         raise ValueError(f"rope_append_: kv_heads = {Hkv} must divide the {H} query heads")
@@ -514,29 +513,45 @@ def rope_append_(qkv: torch.Tensor, table: torch.Tensor, k_cache: torch.Tensor, 
         raise ValueError(f"rope_append_: qkv must be [B*Sq, (H + 2*Hkv)*D] = [{B * Sq}, {width}], got {tuple(qkv.shape)}")
     if tuple(table.shape[1:]) != (D // 2, 2) or table.dtype != torch.float32 or table.device != qkv.device:
         raise ValueError("rope_append_: table must be rope_table(max_positions, D) (fp32 [P, D/2, 2]) on qkv's device")
+    want = torch.float8_e4m3fn if fp8 else qkv.dtype
     if k_cache.dim() != 4 or tuple(k_cache.shape[:2]) != (B, Hkv) or k_cache.shape[3] != D \
-            or v_cache.shape != k_cache.shape or k_cache.dtype != qkv.dtype or v_cache.dtype != qkv.dtype \
+            or v_cache.shape != k_cache.shape or k_cache.dtype != want or v_cache.dtype != want \
             or not (k_cache.is_contiguous() and v_cache.is_contiguous()):
-        raise ValueError(f"rope_append_: k_cache / v_cache must be contiguous [B, Hkv, Smax, D] = [{B}, {Hkv}, Smax, {D}] "
-                         f"of qkv's dtype, got {tuple(k_cache.shape)} / {tuple(v_cache.shape)}")
+        raise ValueError(f"rope_append_: k_cache / v_cache must both be contiguous [B, Hkv, Smax, D] = [{B}, {Hkv}, Smax, {D}] "
+                         f"of {'float8_e4m3fn (an FP8 cache)' if fp8 else 'the dtype of qkv'}, got "
+                         f"{tuple(k_cache.shape)} {k_cache.dtype} / {tuple(v_cache.shape)} {v_cache.dtype}")
+    Smax = k_cache.shape[2]
+    for name, sc in (("k_scale", k_scale), ("v_scale", v_scale)) if fp8 else ():
+        if sc is None or tuple(sc.shape) != (B, Hkv, Smax) or sc.dtype != torch.float32 or not sc.is_contiguous() \
+                or sc.device != k_cache.device:
+            raise ValueError(f"rope_append_: an FP8 cache needs {name}, contiguous fp32 [B, Hkv, Smax] = [{B}, {Hkv}, {Smax}]")
     if kv_len.numel() != B:
         raise ValueError(f"rope_append_: kv_len must hold one length per sequence ({B})")
-    Smax = k_cache.shape[2]
     if overflow is None:
         overflow = torch.zeros(1, dtype=torch.int32, device=qkv.device)
-    if _kernel_dtype(qkv) and D % 16 == 0 and qkv.stride(0) % 8 == 0 and qkv.data_ptr() % 16 == 0:
-        if not _lib.has("dtd_rope_append"):
-            raise _lib.KernelError("the kernel library has no KV-cache append entry point (stale build)")
+    # the kernels' domains: the plain append takes both kernel dtypes and any D % 16; the quantising one bf16, D 64 / 128
+    kernel = (qkv.is_cuda and qkv.dtype == torch.bfloat16 and D in (64, 128)) if fp8 else (_kernel_dtype(qkv) and D % 16 == 0)
+    if kernel and qkv.stride(0) % 8 == 0 and qkv.data_ptr() % 16 == 0:
+        entry = "dtd_rope_append_fp8" if fp8 else "dtd_rope_append"
+        if not _lib.has(entry):
+            raise _lib.KernelError(f"the kernel library has no {'FP8 ' if fp8 else ''}KV-cache append entry point (stale build)")
         table = table.contiguous()
         kv32 = kv_len.reshape(-1).to(device=qkv.device, dtype=torch.int32).contiguous()
-        _lib.call("dtd_rope_append", _lib.dt(qkv), qkv.data_ptr(), table.data_ptr(), k_cache.data_ptr(),
-                  v_cache.data_ptr(), kv32.data_ptr(), overflow.data_ptr(), B, Sq, H, Hkv, D, qkv.stride(0), Smax,
+        head = (qkv.data_ptr(), table.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr())
+        head = (head + (k_scale.data_ptr(), v_scale.data_ptr())) if fp8 else ((_lib.dt(qkv),) + head)
+        _lib.call(entry, *head, kv32.data_ptr(), overflow.data_ptr(), B, Sq, H, Hkv, D, qkv.stride(0), Smax,
                   table.shape[0], _lib.stream())
         return qkv
     slot = kv_len.reshape(B, 1).to(device=qkv.device, dtype=torch.int64) + torch.arange(Sq, device=qkv.device)
     rope_(qkv, table, B, Sq, H, D, pos=slot, kv_heads=Hkv)
     x = qkv.view(B, Sq, H + 2 * Hkv, D)
-    _append_rows_ref(slot, overflow, ((k_cache, x[:, :, H:H + Hkv]), (v_cache, x[:, :, H + Hkv:])))
+    pairs = ((k_cache, x[:, :, H:H + Hkv]), (v_cache, x[:, :, H + Hkv:]))
+    if fp8:
+        from .kv_cache import quantize_kv_ref
+        (kq, ks), (vq, vs) = (quantize_kv_ref(new) for _, new in pairs)
+        pairs = ((k_cache.view(torch.uint8), kq.view(torch.uint8)), (k_scale.unsqueeze(-1), ks.unsqueeze(-1)),
+                 (v_cache.view(torch.uint8), vq.view(torch.uint8)), (v_scale.unsqueeze(-1), vs.unsqueeze(-1)))
+    _append_rows_ref(slot, overflow, pairs)
     return qkv
 
 
@@ -563,52 +578,6 @@ def _append_rows_ref(slot: torch.Tensor, overflow: torch.Tensor, pairs) -> None:
         flat = cache.view(B * Hkv * Smax, W)
         val = torch.where(has, new.transpose(1, 2).gather(2, pick), flat[rows.reshape(-1)].view(B, Hkv, Sq, W))
         flat.index_copy_(0, rows.reshape(-1), val.reshape(-1, W))
-
-
-def _rope_append_fp8_(qkv, table, k_cache, v_cache, k_scale, v_scale, kv_len, B, Sq, H, D, kv_heads, overflow):
-    """``rope_append_`` on FP8 caches (its docstring)."""
-    from .kv_cache import quantize_kv_ref
-    Hkv = H if kv_heads is None else int(kv_heads)
-    if Hkv <= 0 or H % Hkv:
-        raise ValueError(f"rope_append_: kv_heads = {Hkv} must divide the {H} query heads")
-    width = (H + 2 * Hkv) * D
-    if qkv.dim() != 2 or qkv.shape[0] != B * Sq or qkv.shape[1] != width or qkv.stride(1) != 1:
-        raise ValueError(f"rope_append_: qkv must be [B*Sq, (H + 2*Hkv)*D] = [{B * Sq}, {width}], got {tuple(qkv.shape)}")
-    if tuple(table.shape[1:]) != (D // 2, 2) or table.dtype != torch.float32 or table.device != qkv.device:
-        raise ValueError("rope_append_: table must be rope_table(max_positions, D) (fp32 [P, D/2, 2]) on qkv's device")
-    if k_cache.dim() != 4 or tuple(k_cache.shape[:2]) != (B, Hkv) or k_cache.shape[3] != D \
-            or v_cache.shape != k_cache.shape or k_cache.dtype != torch.float8_e4m3fn \
-            or v_cache.dtype != torch.float8_e4m3fn or not (k_cache.is_contiguous() and v_cache.is_contiguous()):
-        raise ValueError(f"rope_append_: FP8 k_cache / v_cache must both be contiguous float8_e4m3fn [B, Hkv, Smax, D] = "
-                         f"[{B}, {Hkv}, Smax, {D}], got {tuple(k_cache.shape)} {k_cache.dtype} / "
-                         f"{tuple(v_cache.shape)} {v_cache.dtype}")
-    Smax = k_cache.shape[2]
-    for name, sc in (("k_scale", k_scale), ("v_scale", v_scale)):
-        if sc is None or tuple(sc.shape) != (B, Hkv, Smax) or sc.dtype != torch.float32 or not sc.is_contiguous() \
-                or sc.device != k_cache.device:
-            raise ValueError(f"rope_append_: an FP8 cache needs {name}, contiguous fp32 [B, Hkv, Smax] = [{B}, {Hkv}, {Smax}]")
-    if kv_len.numel() != B:
-        raise ValueError(f"rope_append_: kv_len must hold one length per sequence ({B})")
-    if overflow is None:
-        overflow = torch.zeros(1, dtype=torch.int32, device=qkv.device)
-    if qkv.is_cuda and qkv.dtype == torch.bfloat16 and D in (64, 128) and qkv.stride(0) % 8 == 0 \
-            and qkv.data_ptr() % 16 == 0:
-        if not _lib.has("dtd_rope_append_fp8"):
-            raise _lib.KernelError("the kernel library has no FP8 KV-cache append entry point (stale build)")
-        table = table.contiguous()
-        kv32 = kv_len.reshape(-1).to(device=qkv.device, dtype=torch.int32).contiguous()
-        _lib.call("dtd_rope_append_fp8", qkv.data_ptr(), table.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                  k_scale.data_ptr(), v_scale.data_ptr(), kv32.data_ptr(), overflow.data_ptr(), B, Sq, H, Hkv, D,
-                  qkv.stride(0), Smax, table.shape[0], _lib.stream())
-        return qkv
-    slot = kv_len.reshape(B, 1).to(device=qkv.device, dtype=torch.int64) + torch.arange(Sq, device=qkv.device)
-    rope_(qkv, table, B, Sq, H, D, pos=slot, kv_heads=Hkv)
-    x = qkv.view(B, Sq, H + 2 * Hkv, D)
-    kq, ks = quantize_kv_ref(x[:, :, H:H + Hkv])
-    vq, vs = quantize_kv_ref(x[:, :, H + Hkv:])
-    _append_rows_ref(slot, overflow, ((k_cache.view(torch.uint8), kq.view(torch.uint8)), (k_scale.unsqueeze(-1), ks.unsqueeze(-1)),
-                                      (v_cache.view(torch.uint8), vq.view(torch.uint8)), (v_scale.unsqueeze(-1), vs.unsqueeze(-1))))
-    return qkv
 
 
 def _swiglu_kernel(t: torch.Tensor, f: int) -> bool:

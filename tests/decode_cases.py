@@ -8,6 +8,7 @@ causal, with ``key_range[b] = (lo_b, n_b)``; sequence b's decoded row is row n_b
 the K / V of all Smax tokens of that prefill, the step's qkv the rows n_b - 1.
 """
 import functools
+import math
 import types
 
 import torch
@@ -27,6 +28,30 @@ WINDOWS = (1, KT, KT + 7)
 
 CAP_BF16, LSE_TOL = 2e-2, 1e-5            # the project's bf16 bounds (tests/test_attention_oracles_cpu.py)
 REF_CTX_TOL, REF_LSE_TOL = 5e-3, 2.5e-6   # ... and a quarter of them: the math reference's
+
+GUARD = 1024          # elements on either side of a guarded slice (a multiple of 16: 16-byte alignment, of codes too)
+SENT, SENT_CODE = -12345.0, 0xA5          # the sentinel of a guarded buffer: floating point, uint8 codes
+
+
+# ------------------------------------------------------------------------------------- guarded buffers (GPU tests)
+def guarded(shape, dtype, fill=None, device="cuda"):
+    """(buffer, slice of ``shape`` out of its middle); the buffer is the sentinel everywhere else."""
+    n = math.prod(shape)
+    sent = SENT_CODE if dtype == torch.uint8 else SENT
+    buf = torch.full((n + 2 * GUARD,), sent, dtype=dtype, device=device)
+    view = buf[GUARD:GUARD + n].view(shape)
+    if fill is not None:
+        view.copy_(fill)
+    return buf, view
+
+
+def guards_intact(buf, n):
+    sent = SENT_CODE if buf.dtype == torch.uint8 else SENT
+    return bool((buf[:GUARD] == sent).all()) and bool((buf[GUARD + n:] == sent).all())
+
+
+def bits(t):
+    return t.contiguous().view({1: torch.uint8, 2: torch.int16, 4: torch.int32}[t.element_size()])
 
 
 def base_cases():

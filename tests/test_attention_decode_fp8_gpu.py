@@ -12,8 +12,6 @@ writes is a slice out of the middle of a larger sentinel-filled one whose guard 
 kernel, every cache and scale slot -- must be unchanged after each call; every slot outside a sequence's
 [lo, hi) holds the NaN code 0x7F and a NaN scale, so a read of a slot that takes no part shows in the result.
 """
-import math
-
 import pytest
 import torch
 
@@ -23,32 +21,11 @@ from distributed_training_and_deepspeed_amd.ops import functional as Fx
 from distributed_training_and_deepspeed_amd.ops.kv_cache import quantize_kv_ref
 
 from . import decode_cases as DC
+from .decode_cases import SENT, SENT_CODE, bits as _bits, guarded as _guarded, guards_intact as _guards_intact
 from .decode_fp8_cases import FP8, dequantized_oracle, quantized_case
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-GUARD = 1024          # elements on either side of a guarded slice (a multiple of 16: 16-byte alignment of the codes)
-SENT, SENT_CODE = -12345.0, 0xA5
-
-
-def _guarded(shape, dtype, fill=None):
-    """(buffer, slice of ``shape`` out of its middle); the buffer is the sentinel everywhere else."""
-    n = math.prod(shape)
-    sent = SENT_CODE if dtype == torch.uint8 else SENT
-    buf = torch.full((n + 2 * GUARD,), sent, dtype=dtype, device=DEV)
-    view = buf[GUARD:GUARD + n].view(shape)
-    if fill is not None:
-        view.copy_(fill)
-    return buf, view
-
-
-def _guards_intact(buf, n):
-    sent = SENT_CODE if buf.dtype == torch.uint8 else SENT
-    return bool((buf[:GUARD] == sent).all()) and bool((buf[GUARD + n:] == sent).all())
-
-
-def _bits(t):
-    return t.contiguous().view({1: torch.uint8, 2: torch.int16, 4: torch.int32}[t.element_size()])
 
 
 # ------------------------------------------------------------------------------------- dtd_rope_append_fp8

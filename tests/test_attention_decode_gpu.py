@@ -11,8 +11,6 @@ out of the middle of larger sentinel-filled buffers whose guard regions -- and e
 unchanged after each call, and every cache slot outside a sequence's [lo, hi) holds NaN, so a read of a slot
 that takes no part shows in the result.
 """
-import math
-
 import pytest
 import torch
 
@@ -21,29 +19,10 @@ from distributed_training_and_deepspeed_amd.ops import attention as A
 from distributed_training_and_deepspeed_amd.ops import functional as Fx
 
 from . import decode_cases as DC
+from .decode_cases import SENT, bits as _bits, guarded as _guarded, guards_intact as _guards_intact
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-GUARD = 1024          # elements on either side of a guarded slice (a multiple of 8: 16-byte alignment)
-SENT = -12345.0
-
-
-def _guarded(shape, dtype, fill=None):
-    """(buffer, slice of ``shape`` out of its middle); the buffer is SENT everywhere else."""
-    n = math.prod(shape)
-    buf = torch.full((n + 2 * GUARD,), SENT, dtype=dtype, device=DEV)
-    view = buf[GUARD:GUARD + n].view(shape)
-    if fill is not None:
-        view.copy_(fill)
-    return buf, view
-
-
-def _guards_intact(buf, n):
-    return bool((buf[:GUARD] == SENT).all()) and bool((buf[GUARD + n:] == SENT).all())
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16 if t.element_size() == 2 else torch.int32)
 
 
 def _poisoned(c):
