@@ -210,3 +210,16 @@ def kv_cache_bytes(cfg, batch: int, max_len: int, dtype=torch.bfloat16, kv_dtype
             raise ValueError(f"kv_dtype must be None, dtype, torch.float8_e4m3fn or 'fp8', got {kv_dtype!r}")
         return rows * (cfg.head_dim + 4)
     return rows * cfg.head_dim * torch.empty((), dtype=dtype).element_size()
+
+
+def weight_bytes_fp8(cfg, head: bool = False) -> int:
+    """Bytes of the FP8 weight codes and their per-row fp32 scales that ``CausalLM.quantize_weights_`` keeps beside
+    the parameters of a Llama-family model (``ops/quant.py``): one byte per element of the four projections of
+    every layer plus four bytes per output row; with ``head`` the untied LM head too.  This is what a decode
+    step streams instead of two bytes per element; the bf16 parameters stay resident."""
+    h, f = cfg.hidden_size, cfg.ffn_size
+    shapes = [((cfg.num_heads + 2 * cfg.kv_heads) * cfg.head_dim, h), (h, h), (2 * f, h), (h, f)]
+    n = cfg.num_layers * sum(r * c + 4 * r for r, c in shapes)
+    if head:
+        n += cfg.vocab_size * h + 4 * cfg.vocab_size
+    return n

@@ -49,6 +49,7 @@ from .llama import LlamaLayer
 from .moe import MoeLlamaLayer
 from ..ops.attention import doc_position_ids, doc_range_from_segment_ids, key_range_from_mask
 from ..ops.kv_cache import KVCache
+from ..ops.quant import check_quantized, clear_quantized_, quantize_params_
 from ..utils.graphs import CAPTURE_ERROR_MODE
 from .transformer import Runtime, TransformerLayer, prefetch_masks, stage_dgrad_transposes
 
@@ -150,6 +151,42 @@ class CausalLM(nn.Module):
             if type(owner).__name__ == "ZeroEngine":
                 raise NotImplementedError("generation needs the whole weights: a ZeRO-wrapped model is not supported")
 
+    # ------------------------------------------------------------------ FP8 weights for the decode steps
+    @torch.no_grad()
+    def quantize_weights_(self, dtype: str = "fp8", head: bool = False) -> "CausalLM":
+        """Put the four projections of every layer (and with ``head`` the untied LM head) on the FP8 grid of
+        ``ops/quant.py`` -- e4m3fn codes with one power-of-two scale per output row -- in place: each parameter
+        takes its dequantised values, which bf16 holds exactly, and the codes and scales become non-persistent
+        buffers beside it (the state dict is unchanged).  The decode steps of the fused path then stream the
+        codes (``ops.gemm.linear_skinny``), half the bytes of the bf16 weights; everything else -- the prefill,
+        training, the reference path, more than 64 sequences -- reads the parameters, which are the same
+        model.  The bf16 parameters stay resident: this buys decode bandwidth, not memory.  Call it on the
+        model in its final dtype and on its final device.  Updating a quantised parameter afterwards makes
+        the next ``decode_step`` raise: quantise again, or ``clear_quantized_weights()``."""
+        if dtype != "fp8":
+            raise ValueError(f"quantize_weights_: only 'fp8' (e4m3fn) is implemented, not {dtype!r}")
+        self._check_generation()
+        if head and self.head.own_weight is None:
+            raise NotImplementedError("quantize_weights_(head=True) needs an untied LM head")
+        for layer in self.layers:
+            layer.quantize_weights_()
+        if head:
+            quantize_params_(self.head, ("own_weight",), self.head._w8_versions)
+        return self
+
+    def clear_quantized_weights(self) -> None:
+        """Drop the FP8 codes and scales; the parameters keep their (dequantised) values."""
+        for layer in self.layers:
+            if isinstance(layer, LlamaLayer):
+                layer.clear_quantized_weights()
+        clear_quantized_(self.head, self.head._w8_versions)
+
+    def _check_quantized(self) -> None:
+        for layer in self.layers:
+            if isinstance(layer, LlamaLayer):
+                layer.check_quantized()
+        check_quantized(self.head, self.head._w8_versions)
+
     @torch.no_grad()
     def prefill(self, input_ids: torch.Tensor, cache: KVCache, attention_mask: torch.Tensor | None = None) -> torch.Tensor:
         """The prompt ``input_ids [B, S0]`` into the EMPTY ``cache``; returns the logits ``[B, V]`` of the last
@@ -188,6 +225,7 @@ class CausalLM(nn.Module):
             raise ValueError("decode_step needs a prefilled cache")
         if cache.filled + 1 > cache.max_len:
             raise ValueError(f"the cache is full ({cache.max_len} positions)")
+        self._check_quantized()    # stale FP8 codes (a parameter updated after quantize_weights_) are an error
         x = self.embeddings(tokens.view(cache.batch, 1))
         for i, layer in enumerate(self.layers):
             x = layer.forward_cached(x, cache, i, False)

@@ -47,6 +47,7 @@ from ..ops import attention as A
 from ..ops import functional as Fx
 from ..ops import gemm as G
 from ..ops.grad import emit_wgrad, grad_done, grad_dst, note_use
+from ..ops.quant import check_quantized, clear_quantized_, quantize_params_
 from .config import TransformerConfig
 from .layers import ref_rms_norm
 from .transformer import Runtime, init_linear_, ref_attn_dropout
@@ -92,6 +93,7 @@ class LlamaLayer(nn.Module):
         for w in (self.qkv_w, self.o_w, self.gu_w, self.down_w):
             init_linear_(w, None)
         self.sid_attn = rt.new_sid()
+        self._w8_versions: dict = {}      # parameter name -> its _version when its FP8 codes were made
 
     def params(self):
         return (self.qkv_w, self.o_w, self.n1_g, self.gu_w, self.down_w, self.n2_g)
@@ -150,9 +152,12 @@ class LlamaLayer(nn.Module):
         fused = rt.use_fused(x)
         eps, window = c.ln_eps, c.sliding_window or None
         x2d = x.reshape(B * Sq, h)
+        # a decode step of the fused path reads the FP8 codes of the projections when the model holds them
+        # (CausalLM.quantize_weights_): the same weights as the parameters, half the bytes
+        proj = self._proj_w8 if fused and not prefill and self.w8 else self._proj
         if fused:
             _, a_in, _ = Fx.rms_fwd(None, x2d, self.n1_g, eps)
-            qkv = _linear(a_in, self.qkv_w)
+            qkv = proj(a_in, "qkv_w")
         else:
             qkv = F.linear(ref_rms_norm(x2d, self.n1_g, eps), self.qkv_w)
         ks, vs = cache.layer_scales(i)      # (None, None) unless the cache is FP8
@@ -169,15 +174,41 @@ class LlamaLayer(nn.Module):
             actx, _ = A.attn_decode_ref(qkv, kc, vc, cache.kv_next, B, H, D, Hkv, window, cache.kv_start,
                                         k_scale=ks, v_scale=vs)
         if fused:
-            o = _linear(actx, self.o_w)
+            o = proj(actx, "o_w")
             z1, f_in, _ = Fx.rms_fwd(o, x2d, self.n2_g, eps)
-            a = Fx.swiglu_fwd(_linear(f_in, self.gu_w))
-            out = Fx.dropout_add(_linear(a, self.down_w), z1, 0.0, rt.rng, 0)
+            a = Fx.swiglu_fwd(proj(f_in, "gu_w"))
+            out = Fx.dropout_add(proj(a, "down_w"), z1, 0.0, rt.rng, 0)
         else:
             z1 = x2d + F.linear(actx, self.o_w)
             g, u = F.linear(ref_rms_norm(z1, self.n2_g, eps), self.gu_w).split(c.ffn_size, -1)
             out = z1 + F.linear(F.silu(g) * u, self.down_w)
         return out.view(B, Sq, h)
+
+    # ------------------------------------------------------------------ FP8 weights for the decode step
+    W8_NAMES = ("qkv_w", "o_w", "gu_w", "down_w")
+
+    @property
+    def w8(self) -> bool:
+        return bool(self._w8_versions)
+
+    def _proj(self, x: torch.Tensor, name: str) -> torch.Tensor:
+        return _linear(x, getattr(self, name))
+
+    def _proj_w8(self, x: torch.Tensor, name: str) -> torch.Tensor:
+        codes, scale = getattr(self, name + "_codes"), getattr(self, name + "_scale")
+        if G.skinny_supported(x.shape[0], codes.shape[0], x.shape[1], x, codes):
+            return G.linear_skinny(x, codes, scale)
+        return self._proj(x, name)       # more than 64 rows: the parameter, which holds the same values
+
+    @torch.no_grad()
+    def quantize_weights_(self) -> None:
+        quantize_params_(self, self.W8_NAMES, self._w8_versions)
+
+    def clear_quantized_weights(self) -> None:
+        clear_quantized_(self, self._w8_versions)
+
+    def check_quantized(self) -> None:
+        check_quantized(self, self._w8_versions)
 
     # ------------------------------------------------------------------ reference path
     def _reference(self, x, key_range, doc_range, position_ids, table):

@@ -286,9 +286,66 @@ def _bias_ok(b) -> bool:
     return b is None or (b.is_cuda and b.dtype == torch.bfloat16 and b.is_contiguous() and b.data_ptr() % 16 == 0)
 
 
+# Skinny products, M <= 64 rows (the decode step's projections: pure weight streaming) on
+# ops/csrc/gemm_skinny.hip: W in 16-byte loads straight into the MFMA's row operand, the waves of a
+# workgroup splitting K, bf16 weights or FP8 codes with one scale per output row (ops/quant.py).
+# Off by default (DTD_GEMM_SKINNY=1 / set_skinny): profiles/gemm_skinny.jsonl has the measurement
+# against the library.  ``linear_skinny`` itself is always available (the FP8 weights have no other path).
+_SKINNY = [os.environ.get("DTD_GEMM_SKINNY", "0") == "1"]
+SKINNY_MAX_M = 64
+FMT_BF16, FMT_FP8 = 0, 1
+
+
+def set_skinny(on: bool) -> None:
+    _SKINNY[0] = bool(on)
+
+
+def skinny_enabled() -> bool:
+    return _SKINNY[0]
+
+
+def _ok8(t: torch.Tensor) -> bool:
+    return (t is not None and t.is_cuda and t.dtype == torch.float8_e4m3fn and t.dim() == 2 and t.stride(1) == 1
+            and t.stride(0) % 16 == 0 and t.data_ptr() % 16 == 0)
+
+
+def skinny_supported(M: int, N: int, K: int, *tensors) -> bool:
+    """Shape and layout contract of ``linear_skinny``: 1 <= M <= 64, N % 16 == 0, K % 128 == 0; the
+    tensors bf16 (or e4m3fn codes), 2-D, K-contiguous with 16-byte aligned rows."""
+    if not (all(_ok(t) or _ok8(t) for t in tensors) and _lib.has("dtd_gemm_skinny")):
+        return False
+    return bool(_lib.lib().dtd_gemm_skinny_supported(M, N, K))
+
+
+def linear_skinny(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor | None = None,
+                  out: torch.Tensor | None = None) -> torch.Tensor:
+    """x [M, K] . w [N, K]^T in bf16, M <= 64.  With ``scale`` (fp32 [N]) ``w`` holds e4m3fn codes and
+    the result is ``scale[n] * sum_k x[m, k] * float(w[n, k])``, rounded to bf16 once.  A missing
+    kernel or an unsupported shape is an error, never another path."""
+    M, K = x.shape
+    N = w.shape[0]
+    if w.shape[1] != K or not skinny_supported(M, N, K, x, w):
+        raise ValueError(f"linear_skinny: unsupported product x {tuple(x.shape)} {x.dtype} . w {tuple(w.shape)} {w.dtype}")
+    fp8 = w.dtype == torch.float8_e4m3fn
+    if fp8 != (scale is not None) or x.dtype != torch.bfloat16:
+        raise ValueError("linear_skinny: FP8 codes come with a scale, bf16 weights without; x is bf16")
+    if fp8 and not (scale.is_cuda and scale.dtype == torch.float32 and scale.shape == (N,) and scale.is_contiguous()):
+        raise ValueError("linear_skinny: scale must be a contiguous fp32 [N] tensor on the GPU")
+    y = torch.empty((M, N), dtype=x.dtype, device=x.device) if out is None else out
+    if y.shape != (M, N) or not _ok(y):
+        raise ValueError(f"linear_skinny: out must be a bf16 [{M}, {N}] tensor with 16-byte aligned rows")
+    _lib.call("dtd_gemm_skinny", FMT_FP8 if fp8 else FMT_BF16, x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0),
+              _lib.ptr(scale), y.data_ptr(), y.stride(0), M, N, K, _lib.stream())
+    return y
+
+
 def linear_any(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor | None = None) -> torch.Tensor:
     """F.linear, or a hand-written kernel: the fp32 one for fp32 operands, the bf16 one-wave-per-SIMD
-    kernel (default) or the 8-wave one (all-native mode), when the shape tiles."""
+    kernel (default) or the 8-wave one (all-native mode), when the shape tiles; the skinny kernel for
+    a bf16 product of at most 64 rows when it is switched on."""
+    if (_SKINNY[0] and b is None and x.dim() == 2 and x.shape[0] <= SKINNY_MAX_M and x.dtype == torch.bfloat16
+            and w.dtype == torch.bfloat16 and skinny_supported(x.shape[0], w.shape[0], x.shape[1], x, w)):
+        return linear_skinny(x, w)
     if (x.dtype == torch.float32 and x.dim() == 2 and f32_supported(x.shape[0], w.shape[0], x.shape[1], x, w)
             and (b is None or _ok1d32(b))):
         return gemm_f32_nt(x, w, b)

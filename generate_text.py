@@ -43,12 +43,21 @@ def main(argv=None):
     ap.add_argument("--dtype", default=None, choices=("bfloat16", "float32"), help="default: bfloat16 on the GPU")
     ap.add_argument("--kv-cache-dtype", default="auto", choices=("auto", "fp8"),
                     help="auto: the cache in the model's dtype; fp8: e4m3fn codes with per-row scales")
+    ap.add_argument("--weight-dtype", default="auto", choices=("auto", "fp8"),
+                    help="fp8: the decode steps stream FP8 codes of the projections (quantize_weights_)")
+    ap.add_argument("--skinny-gemm", action="store_true",
+                    help="bf16 products of at most 64 rows on the weight-streaming kernel (GPU)")
     ap.add_argument("--metrics-json", default="")
     args = ap.parse_args(argv)
 
     dev = torch.device(args.device or ("cuda:0" if torch.cuda.is_available() else "cpu"))
     dtype = getattr(torch, args.dtype) if args.dtype else (torch.bfloat16 if dev.type == "cuda" else torch.float32)
     model = build_model(args.model_name, impl=args.impl, dtype=dtype, device=dev, seed=args.seed).eval()
+    if args.weight_dtype == "fp8":
+        model.quantize_weights_("fp8")
+    if args.skinny_gemm:
+        from distributed_training_and_deepspeed_amd.ops import gemm
+        gemm.set_skinny(True)
     cfg = model.cfg
     B, S0, N = args.batch_size, args.prompt_len, args.max_new_tokens
     ids = torch.randint(3, cfg.vocab_size, (B, S0), generator=torch.Generator().manual_seed(args.seed)).to(dev)

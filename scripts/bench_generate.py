@@ -8,6 +8,8 @@ capture once.  The baseline runs ``model(prefix)`` for the same 112 steps (prefi
 the argmax of the last position.  Each arm is timed twice, interleaved; the whole 128-token call is reported too.
 
 ``--kv-cache-dtype fp8`` runs both ``generate`` arms with the FP8 KV cache (``kv_dtype="fp8"``); the row says so.
+``--weight-dtype fp8`` quantises the projections first (``quantize_weights_``: the decode steps stream FP8 codes),
+``--skinny-gemm`` sends the bf16 products of at most 64 rows to ``gemm_skinny.hip``.
 
 One JSON line per (model, B), appended to --out.
 
@@ -28,6 +30,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from distributed_training_and_deepspeed_amd.models import build_model  # noqa: E402
+from distributed_training_and_deepspeed_amd.ops import gemm as G  # noqa: E402
 
 PROMPT, NEW, SHORT = 128, 128, 16
 
@@ -64,6 +67,10 @@ def main():
     ap.add_argument("--models", type=str, default="llama-160m,tinyllama-1.1b")
     ap.add_argument("--batches", type=str, default="1,8")
     ap.add_argument("--kv-cache-dtype", default="auto", choices=("auto", "fp8"), help="auto: the model's dtype")
+    ap.add_argument("--weight-dtype", default="auto", choices=("auto", "fp8"),
+                    help="fp8: quantize_weights_ -- the decode steps stream FP8 codes of the projections")
+    ap.add_argument("--skinny-gemm", action="store_true", help="bf16 products of at most 64 rows on gemm_skinny.hip")
+    ap.add_argument("--skip-recompute", action="store_true", help="leave the no-cache baseline out")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_generate.py needs a GPU")
@@ -71,6 +78,9 @@ def main():
     kv_dtype = None if args.kv_cache_dtype == "auto" else args.kv_cache_dtype
     for name in args.models.split(","):
         model = build_model(name, impl="fused", dtype=torch.bfloat16, device="cuda", seed=0).eval()
+        if args.weight_dtype == "fp8":
+            model.quantize_weights_("fp8")
+        G.set_skinny(args.skinny_gemm)
         for B in (int(b) for b in args.batches.split(",")):
             g = torch.Generator().manual_seed(B)
             ids = torch.randint(3, model.cfg.vocab_size, (B, PROMPT + NEW), generator=g).cuda()
@@ -81,9 +91,10 @@ def main():
             }
             for fn in arms.values():                      # warm-up of every shape the timed calls use
                 fn(SHORT)
-            recompute(model, ids, PROMPT + SHORT, 4)
+            if not args.skip_recompute:
+                recompute(model, ids, PROMPT + SHORT, 4)
             same = bool(torch.equal(arms["eager"](NEW), arms["graph"](NEW)))
-            runs = {"eager": [], "graph": [], "recompute": []}
+            runs = {"eager": [], "graph": []} if args.skip_recompute else {"eager": [], "graph": [], "recompute": []}
             totals = {"eager": [], "graph": []}
             for _ in range(2):
                 for key, fn in arms.items():
@@ -91,10 +102,12 @@ def main():
                     _, t_short = wall(lambda: fn(SHORT))
                     runs[key].append((t_long - t_short) / steps)
                     totals[key].append(t_long)
-                _, t = wall(lambda: recompute(model, ids, PROMPT + SHORT, steps))
-                runs["recompute"].append(t / steps)
+                if not args.skip_recompute:
+                    _, t = wall(lambda: recompute(model, ids, PROMPT + SHORT, steps))
+                    runs["recompute"].append(t / steps)
             rec = {"case": "generate", "model": model.cfg.name, "B": B, "prompt": PROMPT, "new_tokens": NEW,
-                   "kv_cache_dtype": args.kv_cache_dtype, "steps_timed": steps, "graph_tokens_equal_eager": same}
+                   "kv_cache_dtype": args.kv_cache_dtype, "weight_dtype": args.weight_dtype,
+                   "skinny_gemm": args.skinny_gemm, "steps_timed": steps, "graph_tokens_equal_eager": same}
             for key, r in runs.items():
                 ms = sum(r) / 2 * 1e3
                 rec[f"{key}_ms_per_step"] = round(ms, 4)
@@ -102,7 +115,8 @@ def main():
                 rec[f"{key}_tokens_per_s"] = round(B / (ms * 1e-3), 1)
             for key, r in totals.items():
                 rec[f"{key}_call_ms"] = round(sum(r) / 2 * 1e3, 2)
-            rec["eager_over_recompute"] = round(rec["recompute_ms_per_step"] / rec["eager_ms_per_step"], 2)
+            if not args.skip_recompute:
+                rec["eager_over_recompute"] = round(rec["recompute_ms_per_step"] / rec["eager_ms_per_step"], 2)
             rec["graph_over_eager"] = round(rec["eager_ms_per_step"] / rec["graph_ms_per_step"], 2)
             emit(args.out, rec)
         del model
