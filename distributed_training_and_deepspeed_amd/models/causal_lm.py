@@ -194,6 +194,10 @@ class CausalLM(nn.Module):
         (a 0 after a 1 is a ``ValueError``; checked here, once, on the host); ``cache.kv_start`` becomes each
         sequence's first real position.  Rotary positions are the slots, arange(S0), as in ``forward``.
         Advances the cache by S0."""
+        return self._last_logits(self._prefill_hidden(input_ids, cache, attention_mask)[:, -1])
+
+    def _prefill_hidden(self, input_ids, cache, attention_mask):
+        """``prefill`` up to the last layer's output ``[B, S0, h]``."""
         self._check_generation()
         B, S0 = input_ids.shape
         if cache.filled != 0:
@@ -214,7 +218,7 @@ class CausalLM(nn.Module):
         for i, layer in enumerate(self.layers):
             x = layer.forward_cached(x, cache, i, True, key_range)
         cache.advance(S0)
-        return self._last_logits(x[:, -1])
+        return x
 
     @torch.no_grad()
     def decode_step(self, tokens: torch.Tensor, cache: KVCache) -> torch.Tensor:
@@ -232,6 +236,32 @@ class CausalLM(nn.Module):
         cache.advance(1)
         return self._last_logits(x[:, 0])
 
+    @torch.no_grad()
+    def extend(self, tokens: torch.Tensor, cache: KVCache, last_only: bool = False) -> torch.Tensor:
+        """T more tokens per sequence, ``tokens [B, T]``, on top of a NON-EMPTY ``cache``: a further turn of a
+        conversation, one chunk of a long prompt, the drafted tokens of a speculative step.  Returns the logits
+        ``[B, T, V]`` of the T positions -- ``last_only``: ``[B, V]``, the last position's, the head running on B
+        rows as in ``prefill``.  Token t of sequence b takes the slot ``kv_len[b] + t`` and attends the cache and
+        the chunk's tokens up to itself (``ops.attention.attn_extend``).  Advances the cache by T.  No host
+        synchronisation: as in ``decode_step`` the position is the cache's device counters."""
+        x = self._extend_hidden(tokens, cache)
+        return self._last_logits(x[:, -1] if last_only else x)
+
+    def _extend_hidden(self, tokens, cache):
+        """``extend`` up to the last layer's output ``[B, T, h]``."""
+        B, T = tokens.shape
+        if cache.filled == 0:      # (what generation supports was checked by the prefill that filled it)
+            raise ValueError("extend needs a prefilled cache (an empty one takes prefill)")
+        if B != cache.batch or T == 0 or cache.filled + T > cache.max_len:
+            raise ValueError(f"extend: [{B}, {T}] tokens do not fit a cache of {cache.batch} sequences x {cache.max_len} "
+                             f"positions that holds {cache.filled}")
+        self._check_quantized()    # stale FP8 codes (a parameter updated after quantize_weights_) are an error
+        x = self.embeddings(tokens)
+        for i, layer in enumerate(self.layers):
+            x = layer.forward_cached(x, cache, i, False)
+        cache.advance(T)
+        return x
+
     def _last_logits(self, x: torch.Tensor) -> torch.Tensor:
         if self.final_ln is not None:
             x = self.final_ln(x)
@@ -241,7 +271,8 @@ class CausalLM(nn.Module):
     def generate(self, input_ids: torch.Tensor, max_new_tokens: int, attention_mask: torch.Tensor | None = None,
                  do_sample: bool = False, temperature: float = 1.0, top_k: int = 0, eos_token_id: int | None = None,
                  seed: int = 0, max_len: int | None = None, graph: bool = False,
-                 logits_out: list | None = None, kv_dtype=None, cache_out: list | None = None) -> torch.Tensor:
+                 logits_out: list | None = None, kv_dtype=None, cache_out: list | None = None,
+                 prefill_chunk: int | None = None) -> torch.Tensor:
         """``input_ids [B, S0]`` continued by ``max_new_tokens`` = N tokens: int64 ``[B, S0 + N]``.  Greedy by
         default; ``do_sample``: temperature, then top-k (0 = the whole vocabulary), drawn with a
         ``torch.Generator`` seeded with ``seed``.  ``attention_mask``: a LEFT-padded batch (``prefill``).  After
@@ -256,7 +287,14 @@ class CausalLM(nn.Module):
         ``kv_dtype``: ``"fp8"`` (or ``torch.float8_e4m3fn``) keeps the cache as e4m3fn codes with one fp32 scale per
         row (``KVCache.allocate``): half the bytes and half the decode kernel's traffic, at the quantisation's
         error -- a greedy token may differ from the unquantised cache's.  None: the cache in the model's dtype.
-        ``cache_out``: a list that receives the call's ``KVCache`` (tests)."""
+        ``cache_out``: a list that receives the call's ``KVCache`` (tests).
+
+        ``prefill_chunk`` = C: the prompt goes through the model C tokens at a time, which bounds the activation
+        peak of the prompt pass -- the first min(C, S0) tokens through ``prefill`` (left padding included), the
+        rest through ``extend``, only the last chunk running the head.  A bf16 cache gives the one-piece
+        prefill's logits up to rounding order; with an FP8 cache a chunk attends its own and the earlier chunks'
+        keys and values as quantised, where the one-piece prefill attends the unquantised projection, so the two
+        differ by the quantisation error.  None: the prompt in one piece."""
         self._check_generation()
         B, S0 = input_ids.shape
         N = int(max_new_tokens)
@@ -280,7 +318,7 @@ class CausalLM(nn.Module):
         try:
             out = [input_ids.to(torch.int64)]
             done = torch.zeros(B, dtype=torch.bool, device=dev)
-            logits = self.prefill(input_ids, cache, attention_mask) if N > 0 else None
+            logits = self._prefill_chunked(input_ids, cache, attention_mask, prefill_chunk) if N > 0 else None
             captured = static_tok = None
             for t in range(N):
                 if logits_out is not None:
@@ -312,6 +350,23 @@ class CausalLM(nn.Module):
             return torch.cat(out, 1)
         finally:
             self.train(was_training)
+
+    def _prefill_chunked(self, input_ids, cache, attention_mask, chunk):
+        S0 = input_ids.shape[1]
+        if chunk is not None and (int(chunk) != chunk or chunk < 1):
+            raise ValueError(f"prefill_chunk must be a positive integer (or None), got {chunk!r}")
+        if chunk is None or chunk >= S0:
+            return self.prefill(input_ids, cache, attention_mask)
+        x = self._prefill_hidden(input_ids[:, :chunk], cache, None if attention_mask is None else attention_mask[:, :chunk])
+        if attention_mask is not None:
+            # a sequence padded beyond the first chunk has its first real position in a later one: the whole
+            # mask decides (and is checked as ``prefill`` checks its own)
+            if bool(((attention_mask[:, :-1] != 0) & (attention_mask[:, 1:] == 0)).any()):
+                raise ValueError("generation takes a left-padded attention_mask: a 0 follows a 1")
+            cache.kv_start.copy_(key_range_from_mask(attention_mask)[:, 0])
+        for s in range(chunk, S0, chunk):
+            x = self._extend_hidden(input_ids[:, s:s + chunk], cache)
+        return self._last_logits(x[:, -1])
 
     @staticmethod
     def _select(logits, do_sample, temperature, top_k, gen) -> torch.Tensor:

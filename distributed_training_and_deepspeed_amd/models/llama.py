@@ -134,19 +134,19 @@ class LlamaLayer(nn.Module):
         rotated k rows and the v rows are appended there (``Fx.rope_append_``) and ``cache.kv_len`` is left
         alone -- the caller advances it after the last layer.  ``prefill``: the prompt into an empty cache,
         attention being the training forward's over the prompt itself (``key_range`` for a left-padded
-        one).  Otherwise one token per sequence (Sq = 1) against the cache (``A.attn_decode``).  The fused
+        one).  Otherwise Sq new tokens per sequence against the cache: one (``A.attn_decode``), or several
+        (``A.attn_extend``: the cache's keys and the chunk's own, causal inside the chunk).  The fused
         path runs the kernels of the training forward around it; the reference path the same cache in
         plain PyTorch.
 
         An FP8 cache (``cache.quantized``): the append quantises each row (``ops.kv_cache.quantize_kv_ref``'s law,
         by the quantising kernel on the fused path) and the decode attention reads codes and scales.  The prefill
         appends the prompt's rows the same way, but the prompt's own attention runs on the unquantised qkv: only
-        the decode steps see quantised keys and values."""
+        the decode steps see quantised keys and values -- and so does a chunk of several tokens, its own keys and
+        values included."""
         c, rt = self.cfg, self.rt
         B, Sq, h = x.shape
         H, D, Hkv = c.num_heads, c.head_dim, c.kv_heads
-        if not prefill and Sq != 1:
-            raise ValueError(f"a decode step takes one token per sequence, got {Sq}")
         table = rope_table_for(rt, c, x.device)
         kc, vc = cache.layer(i)
         fused = rt.use_fused(x)
@@ -167,11 +167,18 @@ class LlamaLayer(nn.Module):
             attn = A.attn_fwd if fused else A.attn_fwd_ref
             actx = attn(qkv, B, Sq, H, D, c.causal, key_range=key_range, kv_heads=Hkv if Hkv != H else None,
                         window=window)[0]
-        elif fused:
+        elif fused and Sq == 1:
             actx, _ = A.attn_decode(qkv, kc, vc, cache.kv_next, B, H, D, Hkv, window, cache.kv_start,
                                     splits=cache.splits, workspace=cache.workspace, k_scale=ks, v_scale=vs)
-        else:
+        elif Sq == 1:
             actx, _ = A.attn_decode_ref(qkv, kc, vc, cache.kv_next, B, H, D, Hkv, window, cache.kv_start,
+                                        k_scale=ks, v_scale=vs)
+        elif fused:
+            splits, ws = cache.extend_workspace(Sq)
+            actx, _ = A.attn_extend(qkv, kc, vc, cache.kv_len, B, Sq, H, D, Hkv, window, cache.kv_start,
+                                    splits=splits, workspace=ws, k_scale=ks, v_scale=vs)
+        else:
+            actx, _ = A.attn_extend_ref(qkv, kc, vc, cache.kv_len, B, Sq, H, D, Hkv, window, cache.kv_start,
                                         k_scale=ks, v_scale=vs)
         if fused:
             o = proj(actx, "o_w")

@@ -111,6 +111,9 @@ _SIGS = {
     # (the _fp8 forms, e4m3 codes with per-row fp32 scales: k_scale, v_scale behind the caches; bf16 only, no dtype)
     "dtd_attn_decode_fp8": (I, [P, L, P, P, P, P, P, P, P, L, P, P, L, I, I, I, I, I, I, F, I, P]),
     "dtd_rope_append_fp8": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, L, I, I, P]),
+    # attention_extend.hip (dtd_attn_decode's arguments with T behind B; the _fp8 form likewise)
+    "dtd_attn_extend": (I, [P, L, P, P, P, P, P, L, P, P, L, I, I, I, I, I, I, I, F, I, P]),
+    "dtd_attn_extend_fp8": (I, [P, L, P, P, P, P, P, P, P, L, P, P, L, I, I, I, I, I, I, I, F, I, P]),
     # attention_f32.hip
     "dtd_attn_fwd_f32": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, F, P]),
     "dtd_attn_bwd_f32": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, F, P]),

@@ -739,10 +739,12 @@ def _decode_window(window) -> int:
 _FP8 = torch.float8_e4m3fn
 
 
-def _check_decode(qkv, k_cache, v_cache, kv_len, B, H, Hkv, D, k_scale=None, v_scale=None) -> bool:
-    """Validates a decode call; returns whether the caches are FP8 (e4m3fn codes with per-row scales)."""
-    if qkv.dim() != 2 or tuple(qkv.shape) != (B, (H + 2 * Hkv) * D) or qkv.stride(1) != 1:
-        raise ValueError(f"qkv must be [B, (H + 2*Hkv)*D] = [{B}, {(H + 2 * Hkv) * D}], got {tuple(qkv.shape)}")
+def _check_decode(qkv, k_cache, v_cache, kv_len, B, H, Hkv, D, k_scale=None, v_scale=None, T: int = 1) -> bool:
+    """Validates a decode call (T = 1) or an extend call (T tokens per sequence: B*T rows of qkv); returns whether
+    the caches are FP8 (e4m3fn codes with per-row scales)."""
+    if qkv.dim() != 2 or tuple(qkv.shape) != (B * T, (H + 2 * Hkv) * D) or qkv.stride(1) != 1:
+        rows = "B" if T == 1 else "B*T"
+        raise ValueError(f"qkv must be [{rows}, (H + 2*Hkv)*D] = [{B * T}, {(H + 2 * Hkv) * D}], got {tuple(qkv.shape)}")
     if k_cache.dim() != 4 or tuple(k_cache.shape[:2]) != (B, Hkv) or k_cache.shape[3] != D \
             or v_cache.shape != k_cache.shape:
         raise ValueError(f"k_cache / v_cache must be [B, Hkv, Smax, D] = [{B}, {Hkv}, Smax, {D}], got "
@@ -859,4 +861,143 @@ def attn_decode(qkv, k_cache, v_cache, kv_len, B, H, D, kv_heads=None, window=No
     _lib.call(entry, qkv.data_ptr(), qkv.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), *scales,
               kv_len.data_ptr(), _lib.ptr(kv_start), ctx.data_ptr(), ctx.stride(0), lse.data_ptr(), workspace.data_ptr(),
               workspace.numel(), B, H, Hkv, D, Smax, window, 1.0 / math.sqrt(D), splits, _lib.stream())
+    return ctx, lse
+
+
+# ---------------------------------------------------------------------------------- multi-token cached attention
+# T new tokens per sequence against a non-empty cache (ops/csrc/attention_extend.hip): a further turn of a
+# conversation, one chunk of a chunked prefill, the verification pass of speculative decoding.  ``qkv
+# [B*T, (H + 2*Hkv)*D]`` is the chunk's packed projection, row b*T + t token t of sequence b; its rotated k rows
+# and its v rows are already in the cache at the slots kv_len[b] + t (``functional.rope_append_`` with Sq = T),
+# and ``kv_len`` holds the slots written BEFORE the chunk (``cache.kv_len``, not ``kv_next``).  Query (b, t) sits
+# at position p = kv_len[b] + t and attends lo <= j < hi with hi = min(p + 1, Smax) and
+# lo = max(kv_start[b], 0, hi - W); T = 1 is ``attn_decode``'s range.  A row without a key: ctx = 0, lse = -inf.
+_EXTEND_SLAB = 16             # rows of one MFMA slab
+_EXTEND_ROW_BLOCK = 64        # rows of a workgroup once T * G exceeds a slab
+
+
+def extend_row_blocks(T: int, G: int) -> int:
+    """Workgroups per (sequence, key/value head, split) of the extend kernel: one 16-row slab whose keys the four
+    waves split while T * G <= 16, else blocks of 64 rows (a slab per wave)."""
+    R = T * G
+    return 1 if R <= _EXTEND_SLAB else (R + _EXTEND_ROW_BLOCK - 1) // _EXTEND_ROW_BLOCK
+
+
+def extend_splits(B: int, Hkv: int, Smax: int, T: int, G: int) -> int:
+    """Key splits of an extend call: a function of the shapes only -- never of the cache position -- so the
+    launch sequence is static and can be captured.  As ``decode_splits``: enough workgroups to cover the CUs
+    twice, no split shorter than two key tiles; the row blocks count as workgroups, so a long chunk runs in
+    one split and writes its output itself.  The combine kernel's grid bounds B * T for more than one."""
+    if B * T > 65535:
+        return 1
+    tiles = (Smax + DECODE_KEY_TILE - 1) // DECODE_KEY_TILE
+    wgs = max(1, B * Hkv * extend_row_blocks(T, G))
+    return max(1, min((_DECODE_WORKGROUPS + wgs - 1) // wgs, tiles // 2))
+
+
+def extend_workspace_floats(B: int, T: int, H: int, D: int, splits: int) -> int:
+    """fp32 elements of the extend kernel's split workspace: (m, l, o[D]) per (split, row, head); none for one split."""
+    return splits * B * T * H * (D + 2) if splits > 1 else 0
+
+
+def attn_extend_ref(qkv, k_cache, v_cache, kv_len, B, T, H, D, kv_heads=None, window=None, kv_start=None, scale=None,
+                    k_scale=None, v_scale=None):
+    """Math reference of ``attn_extend``, built like ``attn_decode_ref``: plain PyTorch over the whole cache with
+    the slots outside each row's [lo, hi) masked, softmax in fp32 (fp64 for fp64 inputs), masked slots' V forced
+    to 0, ctx rounded once at the end; an FP8 cache is dequantised first.
+    Returns (ctx [B*T, H*D], lse [B*T, H] fp32)."""
+    Hkv = _kv_heads(kv_heads, H)
+    fp8 = _check_decode(qkv, k_cache, v_cache, kv_len, B, H, Hkv, D, k_scale, v_scale, T)
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    W = _decode_window(window)
+    Smax = k_cache.shape[2]
+    c = _cdt(qkv)
+    dev = qkv.device
+    q = qkv[:, :H * D].reshape(B, T, H, D).transpose(1, 2).to(c)                          # [B, H, T, D]
+    G = H // Hkv
+    if fp8:
+        k_cache, v_cache = k_cache.to(c) * k_scale.to(c).unsqueeze(-1), v_cache.to(c) * v_scale.to(c).unsqueeze(-1)
+    k, v = k_cache.to(c).repeat_interleave(G, 1), v_cache.to(c).repeat_interleave(G, 1)     # [B, H, Smax, D]
+    hi = (kv_len.to(device=dev, dtype=torch.int64).view(B, 1) + torch.arange(T, device=dev).view(1, T) + 1).clamp(max=Smax)
+    lo = torch.zeros_like(hi) if kv_start is None else \
+        kv_start.to(device=dev, dtype=torch.int64).clamp(min=0).view(B, 1).expand(B, T)
+    if W:
+        lo = torch.maximum(lo, hi - W)
+    j = torch.arange(Smax, device=dev).view(1, 1, Smax)
+    outside = ((j < lo.unsqueeze(-1)) | (j >= hi.unsqueeze(-1))).unsqueeze(1)              # [B, 1, T, Smax]
+    s = torch.matmul(q, k.transpose(-1, -2)) * scale                                       # [B, H, T, Smax]
+    s = s.masked_fill(outside, float("-inf"))
+    lse = torch.logsumexp(s, -1)
+    prob = _probs(s, lse)
+    # (0 * a slot no row attends: a never-written slot may hold anything, NaN included -- it takes no part)
+    v = v.masked_fill(outside.all(2, keepdim=True).transpose(-1, -2), 0.0)
+    ctx = torch.matmul(prob, v)                                                            # [B, H, T, D]
+    return (ctx.transpose(1, 2).reshape(B * T, H * D).to(qkv.dtype),
+            lse.transpose(1, 2).reshape(B * T, H).to(torch.float32))
+
+
+def attn_extend(qkv, k_cache, v_cache, kv_len, B, T, H, D, kv_heads=None, window=None, kv_start=None, splits=None,
+                workspace: torch.Tensor | None = None, out: tuple | None = None, k_scale: torch.Tensor | None = None,
+                v_scale: torch.Tensor | None = None):
+    """Attention of T new tokens per sequence against the cache (semantics above).  Returns
+    (ctx [B*T, H*D], lse [B*T, H] fp32).
+
+    One routing rule, ``attn_decode``'s: bf16 on the GPU with D 64 / 128 and H / Hkv <= 8 runs the MFMA extend
+    kernel -- in its FP8 format when the caches are ``float8_e4m3fn`` codes with ``k_scale`` / ``v_scale`` -- and a
+    library without it is an error, not a fallback; everything else runs ``attn_extend_ref``.  ``splits``: override
+    of ``extend_splits``.  ``workspace``: fp32 buffer of at least ``extend_workspace_floats`` elements
+    (``KVCache.extend_workspace``), allocated here when None; one split needs none and touches none.  ``out``:
+    (ctx, lse) tensors to write, of the returned shapes and dtypes, ctx with unit column stride."""
+    Hkv = _kv_heads(kv_heads, H)
+    window = _decode_window(window)
+    T = int(T)
+    if T < 1:
+        raise ValueError(f"T must be >= 1, got {T}")
+    fp8 = _check_decode(qkv, k_cache, v_cache, kv_len, B, H, Hkv, D, k_scale, v_scale, T)
+    if not decode_kernel_supported(qkv, H, Hkv, D):
+        ctx, lse = attn_extend_ref(qkv, k_cache, v_cache, kv_len, B, T, H, D, Hkv, window, kv_start, k_scale=k_scale,
+                                   v_scale=v_scale)
+        if out is not None:
+            out[0].copy_(ctx)
+            out[1].copy_(lse)
+            return out[0], out[1]
+        return ctx, lse
+    entry = "dtd_attn_extend_fp8" if fp8 else "dtd_attn_extend"
+    _require(entry, "FP8 extend" if fp8 else "extend")
+    Smax = k_cache.shape[2]
+    if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise ValueError("k_cache / v_cache must be contiguous [B, Hkv, Smax, D]")
+    if fp8 and not (k_scale.is_contiguous() and v_scale.is_contiguous()):
+        raise ValueError("k_scale / v_scale must be contiguous [B, Hkv, Smax]")
+    tiles = (Smax + DECODE_KEY_TILE - 1) // DECODE_KEY_TILE
+    splits = extend_splits(B, Hkv, Smax, T, H // Hkv) if splits is None else int(splits)
+    if splits < 1:
+        raise ValueError(f"splits must be >= 1, got {splits}")
+    splits = min(splits, tiles)
+    if splits > 1 and B * T > 65535:
+        raise ValueError(f"more than one split needs B * T <= 65535, got {B * T}")
+    need = extend_workspace_floats(B, T, H, D, splits)
+    dev = qkv.device
+    if need == 0:
+        workspace = None
+    elif workspace is None:
+        workspace = torch.empty(need, dtype=torch.float32, device=dev)
+    elif workspace.dtype != torch.float32 or workspace.numel() < need or not workspace.is_contiguous():
+        raise ValueError(f"workspace must be a contiguous fp32 tensor of at least {need} elements")
+    kv_len = kv_len.to(device=dev, dtype=torch.int32).contiguous()
+    kv_start = kv_start.to(device=dev, dtype=torch.int32).contiguous() if kv_start is not None else None
+    if out is None:
+        ctx = torch.empty((B * T, H * D), dtype=qkv.dtype, device=dev)
+        lse = torch.empty((B * T, H), dtype=torch.float32, device=dev)
+    else:
+        ctx, lse = out
+        if tuple(ctx.shape) != (B * T, H * D) or ctx.dtype != qkv.dtype or ctx.stride(1) != 1 or ctx.stride(0) % 4 \
+                or ctx.device != dev or tuple(lse.shape) != (B * T, H) or lse.dtype != torch.float32 \
+                or not lse.is_contiguous() or lse.device != dev:
+            raise ValueError(f"out must be (ctx [{B * T}, {H * D}] {qkv.dtype}, lse [{B * T}, {H}] fp32, contiguous) on {dev}")
+    scales = (k_scale.data_ptr(), v_scale.data_ptr()) if fp8 else ()
+    _lib.call(entry, qkv.data_ptr(), qkv.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), *scales,
+              kv_len.data_ptr(), _lib.ptr(kv_start), ctx.data_ptr(), ctx.stride(0), lse.data_ptr(), _lib.ptr(workspace),
+              0 if workspace is None else workspace.numel(), B, T, H, Hkv, D, Smax, window, 1.0 / math.sqrt(D), splits,
+              _lib.stream())
     return ctx, lse

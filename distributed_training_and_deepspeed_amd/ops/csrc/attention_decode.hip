@@ -34,12 +34,13 @@
 //     the reduction are one text.  LDS serves only the reduction over the lane groups at the end, which
 //     writes the split's fp32 partial (m in log2 units, l, o[D]) per query head into the workspace
 //     ws [splits][B][H][D + 2].  A split without a key writes (-inf, 0, 0) and returns.
-//   * decode_combine_kernel, grid (H, B), D threads: merges the splits in index order, writes ctx in
-//     the model's dtype and lse.
+//   * decode_combine_kernel (attention_combine.h), grid (H, B), D threads: merges the splits in index
+//     order, writes ctx in the model's dtype and lse.
 // Every load address is clamped into [lo, hi), hi <= Smax, so no slot outside the cache -- and no slot
 // that was never written -- is read, whatever kv_len / kv_start hold.  All index arithmetic is 64-bit.
 #include <type_traits>
 
+#include "attention_combine.h"
 #include "common.h"
 
 using namespace dtd;
@@ -49,7 +50,6 @@ namespace {
 constexpr int kKeyTile = 64;
 constexpr int kMaxGroup = 8;
 constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
 
 template <int CTRL>
 __device__ __forceinline__ float dpp_f(float v) {
@@ -239,8 +239,6 @@ struct DecodeArgs {
   const float* ks;    // the FP8 cache's row scales [B, Hkv, Smax]; nullptr for bf16
   const float* vs;
 };
-
-__device__ __forceinline__ float fexp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
 // N packed bf16 pairs: a lane's part of a K row as the dot product takes it.
 template <int N>
@@ -507,27 +505,6 @@ __global__ void __launch_bounds__(256) decode_split_kernel(const DecodeArgs a) {
       }
     }
   }
-}
-
-template <int D>
-__global__ void __launch_bounds__(D) decode_combine_kernel(const float* __restrict__ ws, int splits, int B, int H,
-                                                           bf16* __restrict__ ctx, long long ldo,
-                                                           float* __restrict__ lse) {
-  const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
-  const size_t stride = (size_t)B * H * (D + 2);
-  const float* p = ws + ((size_t)b * H + h) * (D + 2);
-  float M = -INFINITY;
-  for (int s = 0; s < splits; ++s) M = fmaxf(M, p[s * stride]);
-  const float Ms = M == -INFINITY ? 0.f : M;
-  float L = 0.f, acc = 0.f;
-  for (int s = 0; s < splits; ++s) {
-    const float w = fexp2(p[s * stride] - Ms);
-    L += w * p[s * stride + 1];
-    acc += w * p[s * stride + 2 + d];
-  }
-  const bool live = L > 0.f;
-  ctx[(size_t)b * ldo + (size_t)h * D + d] = (bf16)(live ? acc / L : 0.f);
-  if (d == 0) lse[(size_t)b * H + h] = live ? M * kLn2 + logf(L) : -INFINITY;
 }
 
 template <int D, bool FP8>

@@ -61,13 +61,16 @@ def _kv_dtype(kv_dtype, dtype):
 
 
 class KVCache:
-    def __init__(self, k, v, kv_len, kv_next, kv_start, overflow, workspace, splits, k_scale=None, v_scale=None):
+    def __init__(self, k, v, kv_len, kv_next, kv_start, overflow, workspace, splits, k_scale=None, v_scale=None,
+                 num_heads=None):
         self.k, self.v = k, v                      # [L, B, Hkv, Smax, D]
         self.k_scale, self.v_scale = k_scale, v_scale      # FP8 cache: fp32 [L, B, Hkv, Smax]; else None
         self.kv_len, self.kv_next, self.kv_start, self.overflow = kv_len, kv_next, kv_start, overflow
         self.filled = 0                            # host mirror of kv_len (every sequence advances alike)
         self.workspace, self.splits = workspace, splits
+        self._extend_ws, self._extend_t = None, 0  # the extend kernel's split workspace: see extend_workspace
         self.num_layers, self.batch, self.kv_heads, self.max_len, self.head_dim = k.shape
+        self.num_heads = num_heads or self.kv_heads        # query heads (the extend workspace's size)
 
     @classmethod
     def allocate(cls, cfg, batch: int, max_len: int, device, dtype, kv_dtype=None) -> "KVCache":
@@ -93,7 +96,7 @@ class KVCache:
         ws = torch.empty(A.decode_workspace_floats(batch, cfg.num_heads, D, splits), dtype=torch.float32, device=device)
         ints = torch.zeros((4, batch), dtype=torch.int32, device=device)
         ints[1].fill_(1)
-        cache = cls(k, v, ints[0], ints[1], ints[2], ints[3, :1], ws, splits, k_scale, v_scale)
+        cache = cls(k, v, ints[0], ints[1], ints[2], ints[3, :1], ws, splits, k_scale, v_scale, cfg.num_heads)
         assert cache.nbytes() == kv_cache_bytes(cfg, batch, max_len, dtype, FP8 if fp8 else None)
         return cache
 
@@ -117,6 +120,22 @@ class KVCache:
         self.kv_len.add_(n)
         self.kv_next.add_(n)
         self.filled += n
+
+    def extend_workspace(self, T: int):
+        """(splits, workspace) of ``ops.attention.attn_extend`` for chunks of T tokens per sequence.  The workspace is
+        allocated on first use, for the largest T seen, and kept (None while no T seen needs one: a single split
+        writes its output itself).  A captured step calls this once before the capture, so the capture allocates
+        nothing."""
+        H = self.num_heads
+        splits = A.extend_splits(self.batch, self.kv_heads, self.max_len, T, H // self.kv_heads)
+        if T > self._extend_t:
+            # the largest need of any chunk length up to T: splits fall as T grows, the rows rise
+            need = max(A.extend_workspace_floats(self.batch, t, H, self.head_dim, A.extend_splits(
+                self.batch, self.kv_heads, self.max_len, t, H // self.kv_heads)) for t in range(1, T + 1))
+            if need and (self._extend_ws is None or self._extend_ws.numel() < need):
+                self._extend_ws = torch.empty(need, dtype=torch.float32, device=self.k.device)
+            self._extend_t = T
+        return splits, self._extend_ws
 
     def layer(self, i: int):
         """(K, V) ``[B, Hkv, Smax, D]`` of layer i."""

@@ -47,6 +47,8 @@ def main(argv=None):
                     help="fp8: the decode steps stream FP8 codes of the projections (quantize_weights_)")
     ap.add_argument("--skinny-gemm", action="store_true",
                     help="bf16 products of at most 64 rows on the weight-streaming kernel (GPU)")
+    ap.add_argument("--prefill-chunk", type=int, default=None,
+                    help="prompt tokens per pass: the prompt goes through the model in chunks (prefill, then extend)")
     ap.add_argument("--metrics-json", default="")
     args = ap.parse_args(argv)
 
@@ -62,7 +64,7 @@ def main(argv=None):
     B, S0, N = args.batch_size, args.prompt_len, args.max_new_tokens
     ids = torch.randint(3, cfg.vocab_size, (B, S0), generator=torch.Generator().manual_seed(args.seed)).to(dev)
     kw = dict(do_sample=args.sample, temperature=args.temperature, top_k=args.top_k, seed=args.seed, graph=args.graph,
-              kv_dtype=None if args.kv_cache_dtype == "auto" else args.kv_cache_dtype)
+              kv_dtype=None if args.kv_cache_dtype == "auto" else args.kv_cache_dtype, prefill_chunk=args.prefill_chunk)
 
     def timed(n):
         _sync(dev)
