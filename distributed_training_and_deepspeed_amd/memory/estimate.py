@@ -223,3 +223,14 @@ def weight_bytes_fp8(cfg, head: bool = False) -> int:
     if head:
         n += cfg.vocab_size * h + 4 * cfg.vocab_size
     return n
+
+
+def weight_bytes_mx4(cfg, head: bool = False) -> int:
+    """``weight_bytes_fp8`` for ``quantize_weights_("mxfp4")``: half a byte per element plus one e8m0 scale byte
+    per block of 32 inputs, N K / 2 + N K / 32 bytes per [N, K] weight (4.25 bits per weight)."""
+    h, f = cfg.hidden_size, cfg.ffn_size
+    shapes = [((cfg.num_heads + 2 * cfg.kv_heads) * cfg.head_dim, h), (h, h), (2 * f, h), (h, f)]
+    n = cfg.num_layers * sum(r * c // 2 + r * c // 32 for r, c in shapes)
+    if head:
+        n += cfg.vocab_size * h // 2 + cfg.vocab_size * h // 32
+    return n

@@ -49,7 +49,7 @@ from .llama import LlamaLayer
 from .moe import MoeLlamaLayer
 from ..ops.attention import doc_position_ids, doc_range_from_segment_ids, key_range_from_mask
 from ..ops.kv_cache import KVCache
-from ..ops.quant import check_quantized, clear_quantized_, quantize_params_
+from ..ops.quant import FORMATS as QUANT_FORMATS, check_quantized, clear_quantized_, quantize_params_
 from ..utils.graphs import CAPTURE_ERROR_MODE
 from .transformer import Runtime, TransformerLayer, prefetch_masks, stage_dgrad_transposes
 
@@ -162,16 +162,22 @@ class CausalLM(nn.Module):
         training, the reference path, more than 64 sequences -- reads the parameters, which are the same
         model.  The bf16 parameters stay resident: this buys decode bandwidth, not memory.  Call it on the
         model in its final dtype and on its final device.  Updating a quantised parameter afterwards makes
-        the next ``decode_step`` raise: quantise again, or ``clear_quantized_weights()``."""
-        if dtype != "fp8":
-            raise ValueError(f"quantize_weights_: only 'fp8' (e4m3fn) is implemented, not {dtype!r}")
+        the next ``decode_step`` raise: quantise again, or ``clear_quantized_weights()``.
+
+        ``dtype="mxfp4"``: the same contract on the MX4 grid -- e2m1 codes, two to a byte, with one power-of-two
+        e8m0 scale per block of 32 consecutive inputs, 4.25 bits per weight (``ops.gemm.linear_skinny_mx4``).
+        Weight-only: the activations stay bf16."""
+        if dtype not in QUANT_FORMATS:
+            raise ValueError(f"quantize_weights_: 'fp8' (e4m3fn) and 'mxfp4' are implemented, not {dtype!r}")
         self._check_generation()
         if head and self.head.own_weight is None:
             raise NotImplementedError("quantize_weights_(head=True) needs an untied LM head")
+        self.clear_quantized_weights()      # (a head quantised earlier in another format does not linger)
         for layer in self.layers:
-            layer.quantize_weights_()
+            layer.quantize_weights_(dtype)
         if head:
-            quantize_params_(self.head, ("own_weight",), self.head._w8_versions)
+            quantize_params_(self.head, ("own_weight",), self.head._w8_versions, dtype)
+            self.head._w8_format = dtype
         return self
 
     def clear_quantized_weights(self) -> None:
@@ -185,7 +191,7 @@ class CausalLM(nn.Module):
         for layer in self.layers:
             if isinstance(layer, LlamaLayer):
                 layer.check_quantized()
-        check_quantized(self.head, self.head._w8_versions)
+        check_quantized(self.head, self.head._w8_versions, self.head._w8_format)
 
     @torch.no_grad()
     def prefill(self, input_ids: torch.Tensor, cache: KVCache, attention_mask: torch.Tensor | None = None) -> torch.Tensor:

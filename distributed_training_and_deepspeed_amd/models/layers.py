@@ -494,7 +494,8 @@ class LMHead(nn.Module):
             self.own_weight = nn.Parameter(torch.empty(cfg.vocab_size, cfg.hidden_size))
             init_linear_(self.own_weight, None)
             self._tied = None
-        self._w8_versions: dict = {}      # "own_weight" -> its _version when its FP8 codes were made
+        self._w8_versions: dict = {}      # "own_weight" -> its _version when its FP8 / MX4 codes were made
+        self._w8_format = "fp8"           # the format of those codes (ops/quant.py)
 
     @property
     def weight(self):
@@ -505,10 +506,14 @@ class LMHead(nn.Module):
         return self.loss(x, labels) if labels is not None else self.logits(x)
 
     def logits(self, x):
-        # the untied head's FP8 codes (CausalLM.quantize_weights_(head=True)): the decode step's B rows
-        if (self._w8_versions and x.dim() == 2 and self.rt.use_fused(x)
-                and G.skinny_supported(x.shape[0], self.own_weight_codes.shape[0], x.shape[1], x, self.own_weight_codes)):
-            return G.linear_skinny(x, self.own_weight_codes, self.own_weight_scale)
+        # the untied head's FP8 or MX4 codes (CausalLM.quantize_weights_(head=True)): the decode step's B rows
+        if self._w8_versions and x.dim() == 2 and self.rt.use_fused(x):
+            codes, scale = self.own_weight_codes, self.own_weight_scale
+            if self._w8_format == "mxfp4":
+                if G.skinny_mx4_supported(x.shape[0], codes.shape[0], x.shape[1], x, codes):
+                    return G.linear_skinny_mx4(x, codes, scale)
+            elif G.skinny_supported(x.shape[0], codes.shape[0], x.shape[1], x, codes):
+                return G.linear_skinny(x, codes, scale)
         return F.linear(x, self.weight)
 
     def loss(self, x: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:

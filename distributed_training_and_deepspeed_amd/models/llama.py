@@ -93,7 +93,8 @@ class LlamaLayer(nn.Module):
         for w in (self.qkv_w, self.o_w, self.gu_w, self.down_w):
             init_linear_(w, None)
         self.sid_attn = rt.new_sid()
-        self._w8_versions: dict = {}      # parameter name -> its _version when its FP8 codes were made
+        self._w8_versions: dict = {}      # parameter name -> its _version when its FP8 / MX4 codes were made
+        self._w8_format = "fp8"           # the format of those codes (ops/quant.py)
 
     def params(self):
         return (self.qkv_w, self.o_w, self.n1_g, self.gu_w, self.down_w, self.n2_g)
@@ -203,19 +204,23 @@ class LlamaLayer(nn.Module):
 
     def _proj_w8(self, x: torch.Tensor, name: str) -> torch.Tensor:
         codes, scale = getattr(self, name + "_codes"), getattr(self, name + "_scale")
-        if G.skinny_supported(x.shape[0], codes.shape[0], x.shape[1], x, codes):
+        if self._w8_format == "mxfp4":
+            if G.skinny_mx4_supported(x.shape[0], codes.shape[0], x.shape[1], x, codes):
+                return G.linear_skinny_mx4(x, codes, scale)
+        elif G.skinny_supported(x.shape[0], codes.shape[0], x.shape[1], x, codes):
             return G.linear_skinny(x, codes, scale)
         return self._proj(x, name)       # more than 64 rows: the parameter, which holds the same values
 
     @torch.no_grad()
-    def quantize_weights_(self) -> None:
-        quantize_params_(self, self.W8_NAMES, self._w8_versions)
+    def quantize_weights_(self, fmt: str = "fp8") -> None:
+        quantize_params_(self, self.W8_NAMES, self._w8_versions, fmt)
+        self._w8_format = fmt
 
     def clear_quantized_weights(self) -> None:
         clear_quantized_(self, self._w8_versions)
 
     def check_quantized(self) -> None:
-        check_quantized(self, self._w8_versions)
+        check_quantized(self, self._w8_versions, self._w8_format)
 
     # ------------------------------------------------------------------ reference path
     def _reference(self, x, key_range, doc_range, position_ids, table):

@@ -129,6 +129,9 @@ _SIGS = {
     # gemm_skinny.hip (format, x, ldx, w, ldw, scale or null, y, ldy, M, N, K)
     "dtd_gemm_skinny_supported": (I, [I, I, I]),
     "dtd_gemm_skinny": (I, [I, P, I, P, I, P, P, I, I, I, I, P]),
+    # gemm_skinny_mx4.hip (x, ldx, codes, ldc, scales, lds, y, ldy, M, N, K)
+    "dtd_gemm_skinny_mx4_supported": (I, [I, I, I]),
+    "dtd_gemm_skinny_mx4": (I, [P, I, P, I, P, I, P, I, I, I, I, P]),
     "dtd_gemm_bt_part_rows": (I, [I]),
     "dtd_gemm_bt": (I, [I, P, I, P, I, P, I, P, P, I, P, P, I, I, I, P, P]),
     "dtd_spin_occupy": (I, [I, ctypes.c_double, P]),

@@ -339,6 +339,45 @@ def linear_skinny(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor | None =
     return y
 
 
+# The same product on MXFP4 weights (ops/csrc/gemm_skinny_mx4.hip; the law and the layout: ops/quant.py): codes
+# uint8 [N, K / 2], two e2m1 elements per byte, and e8m0 scale bytes uint8 [N, K / 32], one per block of 32 k.
+SKINNY_MX4_MAX_SLABS = 8      # the kernel's largest count of 16-row slabs per workgroup (at M <= 16)
+
+
+def _ok_u8(t: torch.Tensor, row_align: int) -> bool:
+    return (t is not None and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and t.stride(1) == 1
+            and t.stride(0) % row_align == 0)
+
+
+def skinny_mx4_supported(M: int, N: int, K: int, *tensors) -> bool:
+    """Shape and layout contract of ``linear_skinny_mx4``: 1 <= M <= 64, N % 16 == 0, K % 128 == 0; the
+    tensors bf16 (x, out) or uint8 codes, 2-D, K-contiguous with 16-byte aligned rows."""
+    if not (all(_ok(t) or (_ok_u8(t, 16) and t.data_ptr() % 16 == 0) for t in tensors) and _lib.has("dtd_gemm_skinny_mx4")):
+        return False
+    return bool(_lib.lib().dtd_gemm_skinny_mx4_supported(M, N, K))
+
+
+def linear_skinny_mx4(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor,
+                      out: torch.Tensor | None = None) -> torch.Tensor:
+    """x [M, K] bf16 against MXFP4 weights, M <= 64: ``sum_k x[m, k] * e2m1(code[n, k]) * 2^(scales[n, k // 32] -
+    127)`` in fp32, rounded to bf16 once.  A missing kernel or an unsupported shape is an error, never another
+    path."""
+    M, K = x.shape
+    N = codes.shape[0]
+    if codes.dtype != torch.uint8 or x.dtype != torch.bfloat16:
+        raise ValueError(f"linear_skinny_mx4: x is bf16 and the codes uint8, got {x.dtype} and {codes.dtype}")
+    if codes.shape[1] * 2 != K or not skinny_mx4_supported(M, N, K, x, codes):
+        raise ValueError(f"linear_skinny_mx4: unsupported product x {tuple(x.shape)} . codes {tuple(codes.shape)}")
+    if not (_ok_u8(scales, 1) and tuple(scales.shape) == (N, K // 32) and scales.is_contiguous()):
+        raise ValueError(f"linear_skinny_mx4: scales must be a contiguous uint8 [{N}, {K // 32}] tensor on the GPU")
+    y = torch.empty((M, N), dtype=x.dtype, device=x.device) if out is None else out
+    if y.shape != (M, N) or not _ok(y):
+        raise ValueError(f"linear_skinny_mx4: out must be a bf16 [{M}, {N}] tensor with 16-byte aligned rows")
+    _lib.call("dtd_gemm_skinny_mx4", x.data_ptr(), x.stride(0), codes.data_ptr(), codes.stride(0), scales.data_ptr(),
+              scales.stride(0), y.data_ptr(), y.stride(0), M, N, K, _lib.stream())
+    return y
+
+
 def linear_any(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor | None = None) -> torch.Tensor:
     """F.linear, or a hand-written kernel: the fp32 one for fp32 operands, the bf16 one-wave-per-SIMD
     kernel (default) or the 8-wave one (all-native mode), when the shape tiles; the skinny kernel for

@@ -43,8 +43,8 @@ def main(argv=None):
     ap.add_argument("--dtype", default=None, choices=("bfloat16", "float32"), help="default: bfloat16 on the GPU")
     ap.add_argument("--kv-cache-dtype", default="auto", choices=("auto", "fp8"),
                     help="auto: the cache in the model's dtype; fp8: e4m3fn codes with per-row scales")
-    ap.add_argument("--weight-dtype", default="auto", choices=("auto", "fp8"),
-                    help="fp8: the decode steps stream FP8 codes of the projections (quantize_weights_)")
+    ap.add_argument("--weight-dtype", default="auto", choices=("auto", "fp8", "mxfp4"),
+                    help="fp8 / mxfp4: the decode steps stream FP8 or MXFP4 codes of the projections (quantize_weights_)")
     ap.add_argument("--skinny-gemm", action="store_true",
                     help="bf16 products of at most 64 rows on the weight-streaming kernel (GPU)")
     ap.add_argument("--prefill-chunk", type=int, default=None,
@@ -55,8 +55,8 @@ def main(argv=None):
     dev = torch.device(args.device or ("cuda:0" if torch.cuda.is_available() else "cpu"))
     dtype = getattr(torch, args.dtype) if args.dtype else (torch.bfloat16 if dev.type == "cuda" else torch.float32)
     model = build_model(args.model_name, impl=args.impl, dtype=dtype, device=dev, seed=args.seed).eval()
-    if args.weight_dtype == "fp8":
-        model.quantize_weights_("fp8")
+    if args.weight_dtype != "auto":
+        model.quantize_weights_(args.weight_dtype)
     if args.skinny_gemm:
         from distributed_training_and_deepspeed_amd.ops import gemm
         gemm.set_skinny(True)

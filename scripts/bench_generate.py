@@ -8,7 +8,7 @@ capture once.  The baseline runs ``model(prefix)`` for the same 112 steps (prefi
 the argmax of the last position.  Each arm is timed twice, interleaved; the whole 128-token call is reported too.
 
 ``--kv-cache-dtype fp8`` runs both ``generate`` arms with the FP8 KV cache (``kv_dtype="fp8"``); the row says so.
-``--weight-dtype fp8`` quantises the projections first (``quantize_weights_``: the decode steps stream FP8 codes),
+``--weight-dtype fp8`` / ``mxfp4`` quantises the projections first (``quantize_weights_``: the decode steps stream the codes),
 ``--skinny-gemm`` sends the bf16 products of at most 64 rows to ``gemm_skinny.hip``.
 
 One JSON line per (model, B), appended to --out.
@@ -67,8 +67,8 @@ def main():
     ap.add_argument("--models", type=str, default="llama-160m,tinyllama-1.1b")
     ap.add_argument("--batches", type=str, default="1,8")
     ap.add_argument("--kv-cache-dtype", default="auto", choices=("auto", "fp8"), help="auto: the model's dtype")
-    ap.add_argument("--weight-dtype", default="auto", choices=("auto", "fp8"),
-                    help="fp8: quantize_weights_ -- the decode steps stream FP8 codes of the projections")
+    ap.add_argument("--weight-dtype", default="auto", choices=("auto", "fp8", "mxfp4"),
+                    help="fp8 / mxfp4: quantize_weights_ -- the decode steps stream FP8 or MXFP4 codes of the projections")
     ap.add_argument("--skinny-gemm", action="store_true", help="bf16 products of at most 64 rows on gemm_skinny.hip")
     ap.add_argument("--skip-recompute", action="store_true", help="leave the no-cache baseline out")
     args = ap.parse_args()
@@ -78,8 +78,8 @@ def main():
     kv_dtype = None if args.kv_cache_dtype == "auto" else args.kv_cache_dtype
     for name in args.models.split(","):
         model = build_model(name, impl="fused", dtype=torch.bfloat16, device="cuda", seed=0).eval()
-        if args.weight_dtype == "fp8":
-            model.quantize_weights_("fp8")
+        if args.weight_dtype != "auto":
+            model.quantize_weights_(args.weight_dtype)
         G.set_skinny(args.skinny_gemm)
         for B in (int(b) for b in args.batches.split(",")):
             g = torch.Generator().manual_seed(B)
