@@ -160,7 +160,8 @@ class CausalLM(nn.Module):
         buffers beside it (the state dict is unchanged).  The decode steps of the fused path then stream the
         codes (``ops.gemm.linear_skinny``), half the bytes of the bf16 weights; everything else -- the prefill,
         training, the reference path, more than 64 sequences -- reads the parameters, which are the same
-        model.  The bf16 parameters stay resident: this buys decode bandwidth, not memory.  Call it on the
+        model -- unless ``set_fp8_activations(True)`` sends the products of more than 64 rows to the FP8 GEMM.
+        The bf16 parameters stay resident: this buys decode bandwidth (and prompt compute), not memory.  Call it on the
         model in its final dtype and on its final device.  Updating a quantised parameter afterwards makes
         the next ``decode_step`` raise: quantise again, or ``clear_quantized_weights()``.
 
@@ -181,11 +182,35 @@ class CausalLM(nn.Module):
         return self
 
     def clear_quantized_weights(self) -> None:
-        """Drop the FP8 codes and scales; the parameters keep their (dequantised) values."""
+        """Drop the FP8 codes and scales; the parameters keep their (dequantised) values.  FP8 activations, which
+        need the codes, are switched off."""
         for layer in self.layers:
             if isinstance(layer, LlamaLayer):
                 layer.clear_quantized_weights()
+                layer._a8 = False
         clear_quantized_(self.head, self.head._w8_versions)
+        self.head._a8 = False
+
+    def set_fp8_activations(self, on: bool) -> "CausalLM":
+        """With FP8 weight codes on the layers (``quantize_weights_("fp8")``): every projection of more than 64 rows
+        -- the prompt pass, an ``extend`` chunk with B T > 64, a batch of more than 64 sequences, and with a
+        quantised head the logits of more than 64 positions -- quantises its input per row by the weight law
+        (``ops.quant.quantize_act_fp8``, one power-of-two scale per token) and multiplies codes by codes on the
+        FP8 MFMA (``ops.gemm.linear_w8a8``), where the shape allows it (N % 16 == 0, K % 128 == 0).  Those passes
+        are then no longer the bf16 model on the weight grid: they differ from it by the activation quantisation.
+        Products of at most 64 rows keep the weight-only kernel and unquantised activations.  The reference path
+        applies the same rule in PyTorch.  Without FP8 codes (none, or MXFP4 ones) a ``ValueError``."""
+        layers = [layer for layer in self.layers if isinstance(layer, LlamaLayer)]
+        if on and not (layers and all(layer.w8 and layer._w8_format == "fp8" for layer in layers)):
+            raise ValueError("set_fp8_activations needs FP8 weight codes on the layers: call quantize_weights_('fp8') first")
+        for layer in layers:
+            layer._a8 = bool(on)
+        self.head._a8 = bool(on) and bool(self.head._w8_versions) and self.head._w8_format == "fp8"
+        return self
+
+    @property
+    def fp8_activations(self) -> bool:
+        return any(getattr(layer, "_a8", False) for layer in self.layers)
 
     def _check_quantized(self) -> None:
         for layer in self.layers:
@@ -211,6 +236,8 @@ class CausalLM(nn.Module):
         if B != cache.batch or S0 > cache.max_len or S0 == 0:
             raise ValueError(f"prefill: a [{B}, {S0}] prompt does not fit a cache of {cache.batch} sequences x "
                              f"{cache.max_len} positions")
+        if self.fp8_activations:
+            self._check_quantized()    # the prompt reads the codes too: stale ones are an error
         key_range = None
         if attention_mask is not None:
             if attention_mask.shape != input_ids.shape:
@@ -300,7 +327,12 @@ class CausalLM(nn.Module):
         rest through ``extend``, only the last chunk running the head.  A bf16 cache gives the one-piece
         prefill's logits up to rounding order; with an FP8 cache a chunk attends its own and the earlier chunks'
         keys and values as quantised, where the one-piece prefill attends the unquantised projection, so the two
-        differ by the quantisation error.  None: the prompt in one piece."""
+        differ by the quantisation error.  None: the prompt in one piece.
+
+        After ``quantize_weights_("fp8")`` and ``set_fp8_activations(True)`` the prompt pass (and every chunk of
+        more than 64 rows) runs its projections on the FP8 GEMM with activations quantised per token: its logits
+        differ from the weight-only model's by that quantisation; the decode steps of at most 64 sequences do not
+        change."""
         self._check_generation()
         B, S0 = input_ids.shape
         N = int(max_new_tokens)

@@ -27,6 +27,7 @@ from torch import nn
 from ..ops import functional as Fx
 from ..ops import gemm as G
 from ..ops.grad import emit_wgrad, gemm_into, grad_done, grad_dst, note_use, wgrad_rows_into
+from ..ops.quant import dequantize_weight, quantize_act_fp8
 
 from .config import TransformerConfig
 from .transformer import Runtime, init_linear_, ref_dropout
@@ -482,6 +483,14 @@ class _LMHeadFusedFn(torch.autograd.Function):
         return dx32.to(x.dtype), None, None, None
 
 
+def a8_rows(x: torch.Tensor, w: torch.Tensor) -> bool:
+    """The products that take FP8 activations when they are switched on: more than 64 rows (fewer are bandwidth-
+    bound and keep the weight-only skinny kernel) of a shape the FP8 GEMM serves (N % 16 == 0, K % 128 == 0) and
+    is measured to win at (``ops.gemm.fp8_worthwhile``)."""
+    M, N, K = x.shape[0], w.shape[0], x.shape[-1]
+    return x.dim() == 2 and M > G.SKINNY_MAX_M and N % 16 == 0 and K % 128 == 0 and G.fp8_worthwhile(M, N, K)
+
+
 class LMHead(nn.Module):
     def __init__(self, cfg: TransformerConfig, rt: Runtime, word_embeddings: nn.Parameter):
         super().__init__()
@@ -496,6 +505,7 @@ class LMHead(nn.Module):
             self._tied = None
         self._w8_versions: dict = {}      # "own_weight" -> its _version when its FP8 / MX4 codes were made
         self._w8_format = "fp8"           # the format of those codes (ops/quant.py)
+        self._a8 = False                  # FP8 activations above 64 rows (CausalLM.set_fp8_activations)
 
     @property
     def weight(self):
@@ -514,6 +524,17 @@ class LMHead(nn.Module):
                     return G.linear_skinny_mx4(x, codes, scale)
             elif G.skinny_supported(x.shape[0], codes.shape[0], x.shape[1], x, codes):
                 return G.linear_skinny(x, codes, scale)
+        if self._a8 and self._w8_versions:
+            # FP8 activations (CausalLM.set_fp8_activations): the layers' rule (models/llama.py) for more than 64
+            # rows -- all positions of an ``extend`` -- on the FP8 GEMM, or written out on the reference path
+            x2d, codes, scale = x.reshape(-1, x.shape[-1]), self.own_weight_codes, self.own_weight_scale
+            if a8_rows(x2d, codes):
+                if not self.rt.use_fused(x):
+                    x2d = dequantize_weight(*quantize_act_fp8(x2d), x.dtype)
+                    return F.linear(x2d, self.weight).view(x.shape[:-1] + (codes.shape[0],))
+                x2d = x2d.contiguous()
+                if G.fp8_supported(x2d.shape[0], codes.shape[0], x2d.shape[1], x2d, codes):
+                    return G.linear_w8a8(x2d, codes, scale).view(x.shape[:-1] + (codes.shape[0],))
         return F.linear(x, self.weight)
 
     def loss(self, x: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:

@@ -47,9 +47,9 @@ from ..ops import attention as A
 from ..ops import functional as Fx
 from ..ops import gemm as G
 from ..ops.grad import emit_wgrad, grad_done, grad_dst, note_use
-from ..ops.quant import check_quantized, clear_quantized_, quantize_params_
+from ..ops.quant import check_quantized, clear_quantized_, dequantize_weight, quantize_act_fp8, quantize_params_
 from .config import TransformerConfig
-from .layers import ref_rms_norm
+from .layers import a8_rows, ref_rms_norm
 from .transformer import Runtime, init_linear_, ref_attn_dropout
 
 
@@ -95,6 +95,7 @@ class LlamaLayer(nn.Module):
         self.sid_attn = rt.new_sid()
         self._w8_versions: dict = {}      # parameter name -> its _version when its FP8 / MX4 codes were made
         self._w8_format = "fp8"           # the format of those codes (ops/quant.py)
+        self._a8 = False                  # FP8 activations above 64 rows (CausalLM.set_fp8_activations)
 
     def params(self):
         return (self.qkv_w, self.o_w, self.n1_g, self.gu_w, self.down_w, self.n2_g)
@@ -154,13 +155,14 @@ class LlamaLayer(nn.Module):
         eps, window = c.ln_eps, c.sliding_window or None
         x2d = x.reshape(B * Sq, h)
         # a decode step of the fused path reads the FP8 codes of the projections when the model holds them
-        # (CausalLM.quantize_weights_): the same weights as the parameters, half the bytes
-        proj = self._proj_w8 if fused and not prefill and self.w8 else self._proj
+        # (CausalLM.quantize_weights_): the same weights as the parameters, half the bytes.  With FP8 activations
+        # switched on, so does every product of more than 64 rows, the prompt's included (_proj_w8)
+        proj = self._proj_w8 if fused and self.w8 and (self._a8 or not prefill) else self._proj
         if fused:
             _, a_in, _ = Fx.rms_fwd(None, x2d, self.n1_g, eps)
             qkv = proj(a_in, "qkv_w")
         else:
-            qkv = F.linear(ref_rms_norm(x2d, self.n1_g, eps), self.qkv_w)
+            qkv = self._proj_ref(ref_rms_norm(x2d, self.n1_g, eps), "qkv_w")
         ks, vs = cache.layer_scales(i)      # (None, None) unless the cache is FP8
         Fx.rope_append_(qkv, table, kc, vc, cache.kv_len, B, Sq, H, D, kv_heads=Hkv, overflow=cache.overflow,
                         k_scale=ks, v_scale=vs)
@@ -187,9 +189,9 @@ class LlamaLayer(nn.Module):
             a = Fx.swiglu_fwd(proj(f_in, "gu_w"))
             out = Fx.dropout_add(proj(a, "down_w"), z1, 0.0, rt.rng, 0)
         else:
-            z1 = x2d + F.linear(actx, self.o_w)
-            g, u = F.linear(ref_rms_norm(z1, self.n2_g, eps), self.gu_w).split(c.ffn_size, -1)
-            out = z1 + F.linear(F.silu(g) * u, self.down_w)
+            z1 = x2d + self._proj_ref(actx, "o_w")
+            g, u = self._proj_ref(ref_rms_norm(z1, self.n2_g, eps), "gu_w").split(c.ffn_size, -1)
+            out = z1 + self._proj_ref(F.silu(g) * u, "down_w")
         return out.view(B, Sq, h)
 
     # ------------------------------------------------------------------ FP8 weights for the decode step
@@ -209,7 +211,17 @@ class LlamaLayer(nn.Module):
                 return G.linear_skinny_mx4(x, codes, scale)
         elif G.skinny_supported(x.shape[0], codes.shape[0], x.shape[1], x, codes):
             return G.linear_skinny(x, codes, scale)
+        elif self._a8 and a8_rows(x, codes) and G.fp8_supported(x.shape[0], codes.shape[0], x.shape[1], x, codes):
+            return G.linear_w8a8(x, codes, scale)      # codes times codes on the FP8 MFMA
         return self._proj(x, name)       # more than 64 rows: the parameter, which holds the same values
+
+    def _proj_ref(self, x: torch.Tensor, name: str) -> torch.Tensor:
+        """The reference path's projection: with FP8 activations on, a product the FP8 GEMM would take sees its
+        input on the activation grid (ops/quant.py's law, written out in PyTorch)."""
+        w = getattr(self, name)
+        if self._a8 and a8_rows(x, w):
+            x = dequantize_weight(*quantize_act_fp8(x), x.dtype)
+        return F.linear(x, w)
 
     @torch.no_grad()
     def quantize_weights_(self, fmt: str = "fp8") -> None:

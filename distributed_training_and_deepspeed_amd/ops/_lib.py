@@ -132,6 +132,11 @@ _SIGS = {
     # gemm_skinny_mx4.hip (x, ldx, codes, ldc, scales, lds, y, ldy, M, N, K)
     "dtd_gemm_skinny_mx4_supported": (I, [I, I, I]),
     "dtd_gemm_skinny_mx4": (I, [P, I, P, I, P, I, P, I, I, I, I, P]),
+    # gemm_fp8.hip (x codes, ldx, sx, w codes, ldw, sw, y, ldy, M, N, K, tile | x, ldx, codes, ldc, scale, M, K)
+    "dtd_gemm_fp8_supported": (I, [I, I, I]),
+    "dtd_gemm_fp8_tile_m": (I, [I]),
+    "dtd_gemm_fp8": (I, [P, I, P, P, I, P, P, I, I, I, I, I, P]),
+    "dtd_act_quant_fp8": (I, [P, I, P, I, P, I, I, P]),
     "dtd_gemm_bt_part_rows": (I, [I]),
     "dtd_gemm_bt": (I, [I, P, I, P, I, P, I, P, P, I, P, P, I, I, I, P, P]),
     "dtd_spin_occupy": (I, [I, ctypes.c_double, P]),

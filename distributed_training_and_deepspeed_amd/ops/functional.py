@@ -1035,6 +1035,37 @@ def sq_norm(x: torch.Tensor) -> torch.Tensor:
 
 
 # --------------------------------------------------------------------------------------
+# activations onto the FP8 grid (ops/csrc/gemm_fp8.hip; the law: ops/quant.py)
+# --------------------------------------------------------------------------------------
+def act_quant_fp8(x: torch.Tensor, codes_out: torch.Tensor | None = None, scale_out: torch.Tensor | None = None):
+    """``x [M, K]`` bf16 -> (codes float8_e4m3fn [M, K], scale fp32 [M]): bit for bit ``quant.quantize_act_fp8``.
+    On the GPU the kernel's contract is K % 128 == 0 and 16-byte aligned rows; anything else there is an error."""
+    from .quant import quantize_act_fp8
+    if not _on_gpu(x):
+        codes, scale = quantize_act_fp8(x)
+        if codes_out is not None:
+            codes_out.copy_(codes)
+        if scale_out is not None:
+            scale_out.copy_(scale)
+        return (codes if codes_out is None else codes_out), (scale if scale_out is None else scale_out)
+    if not (x.dim() == 2 and x.dtype == torch.bfloat16 and x.shape[1] % 128 == 0 and x.shape[0] >= 1
+            and x.stride(1) == 1 and x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0):
+        raise ValueError(f"act_quant_fp8: x must be bf16 [M, K] with K % 128 == 0 and 16-byte aligned rows, got "
+                         f"{tuple(x.shape)} {x.dtype} strides {tuple(x.stride())}")
+    M, K = x.shape
+    codes = torch.empty((M, K), dtype=torch.float8_e4m3fn, device=x.device) if codes_out is None else codes_out
+    scale = torch.empty((M,), dtype=torch.float32, device=x.device) if scale_out is None else scale_out
+    if not (codes.dtype == torch.float8_e4m3fn and codes.shape == (M, K) and codes.stride(1) == 1
+            and codes.stride(0) % 16 == 0 and codes.data_ptr() % 16 == 0 and codes.device == x.device):
+        raise ValueError("act_quant_fp8: codes_out must be float8_e4m3fn [M, K] with 16-byte aligned rows")
+    if not (scale.dtype == torch.float32 and scale.shape == (M,) and scale.is_contiguous() and scale.device == x.device):
+        raise ValueError("act_quant_fp8: scale_out must be a contiguous fp32 [M] tensor")
+    _lib.call("dtd_act_quant_fp8", x.data_ptr(), x.stride(0), codes.data_ptr(), codes.stride(0), scale.data_ptr(), M, K,
+              _lib.stream())
+    return codes, scale
+
+
+# --------------------------------------------------------------------------------------
 # row softmax (instrumented block, SURVEY.md K3)
 # --------------------------------------------------------------------------------------
 def softmax_fwd(x: torch.Tensor) -> torch.Tensor:

@@ -378,6 +378,81 @@ def linear_skinny_mx4(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor
     return y
 
 
+# FP8 codes times FP8 codes on the FP8 MFMA (ops/csrc/gemm_fp8.hip): the product of more than 64 rows of a model
+# whose weights are FP8 codes and whose activations are quantised per row on the way in (ops/quant.py's law,
+# ``functional.act_quant_fp8``).  Y = bf16((sum_k xc wc) * sx[m] * sw[n]): exact products, fp32 sums, one rounding.
+def fp8_tile_ms() -> tuple[int, ...]:
+    """The M edges of the kernel's tiles, smallest first."""
+    return tuple(int(_lib.lib().dtd_gemm_fp8_tile_m(i)) for i in range(3))
+
+
+def _ok_scale(t: torch.Tensor, n: int) -> bool:
+    return (t is not None and t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (n,) and t.is_contiguous()
+            and t.data_ptr() % 16 == 0)
+
+
+def fp8_supported(M: int, N: int, K: int, *tensors) -> bool:
+    """Shape and layout contract of ``linear_fp8``: M >= 1, N % 16 == 0, K % 128 == 0; the tensors e4m3fn codes
+    (or the bf16 output), 2-D, K-contiguous with 16-byte aligned rows of at most 2^22 bytes."""
+    if not (all((_ok(t) or _ok8(t)) and t.stride(0) <= (1 << 22) for t in tensors) and _lib.has("dtd_gemm_fp8")):
+        return False
+    return bool(_lib.lib().dtd_gemm_fp8_supported(M, N, K))
+
+
+# Which products of more than 64 rows a model with FP8 activations sends here (the models' rule, fused and reference
+# path alike): the GEMM itself beat the library's bf16 product at every shape measured (profiles/gemm_fp8.jsonl,
+# 1.08-1.9x), but the quantising kernel in front of it is a second launch of 5-15 us, and against small products
+# (every projection of TinyLlama at M <= 512, the 4096 x 4096 ones at M <= 128) the pair lost.  So: at least 2^25
+# weights, or at least 2^34 multiply-adds.
+_FP8_MIN = [1 << 25, 1 << 34]
+
+
+def fp8_worthwhile(M: int, N: int, K: int) -> bool:
+    return N * K >= _FP8_MIN[0] or M * N * K >= _FP8_MIN[1]
+
+
+@contextlib.contextmanager
+def fp8_at_any_size():
+    """Within the block every product the FP8 GEMM serves counts as worthwhile (tests on tiny models)."""
+    prev = tuple(_FP8_MIN)
+    _FP8_MIN[:] = [0, 0]
+    try:
+        yield
+    finally:
+        _FP8_MIN[:] = prev
+
+
+def linear_fp8(x_codes: torch.Tensor, x_scale: torch.Tensor, w_codes: torch.Tensor, w_scale: torch.Tensor,
+               out: torch.Tensor | None = None, tile: int = 0) -> torch.Tensor:
+    """``bf16((sum_k float(x_codes[m, k]) float(w_codes[n, k])) * x_scale[m] * w_scale[n])`` for e4m3fn codes ``[M, K]``
+    and ``[N, K]`` with positive fp32 scales ``[M]`` and ``[N]``.  ``tile``: one of ``fp8_tile_ms()`` instead of the
+    shape's own tile (tests).  A missing kernel or an unsupported shape is an error, never another path."""
+    if x_codes.dim() != 2 or w_codes.dim() != 2:
+        raise ValueError("linear_fp8: the codes are [M, K] and [N, K]")
+    M, K = x_codes.shape
+    N = w_codes.shape[0]
+    if (w_codes.shape[1] != K or not (_ok8(x_codes) and _ok8(w_codes)) or not fp8_supported(M, N, K, x_codes, w_codes)):
+        raise ValueError(f"linear_fp8: unsupported product x {tuple(x_codes.shape)} {x_codes.dtype} . "
+                         f"w {tuple(w_codes.shape)} {w_codes.dtype}")
+    if not (_ok_scale(x_scale, M) and _ok_scale(w_scale, N)):
+        raise ValueError(f"linear_fp8: the scales are contiguous fp32 [{M}] and [{N}] tensors on the GPU, 16-byte aligned")
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=x_codes.device) if out is None else out
+    if y.shape != (M, N) or not _ok(y):
+        raise ValueError(f"linear_fp8: out must be a bf16 [{M}, {N}] tensor with 16-byte aligned rows")
+    _lib.call("dtd_gemm_fp8", x_codes.data_ptr(), x_codes.stride(0), x_scale.data_ptr(), w_codes.data_ptr(),
+              w_codes.stride(0), w_scale.data_ptr(), y.data_ptr(), y.stride(0), M, N, K, int(tile), _lib.stream())
+    return y
+
+
+def linear_w8a8(x: torch.Tensor, w_codes: torch.Tensor, w_scale: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """bf16 ``x [M, K]`` against FP8 weight codes: the quantising kernel (one scale per row of x), then ``linear_fp8``."""
+    from .functional import act_quant_fp8
+    if not (x.is_cuda and x.dim() == 2):
+        raise ValueError("linear_w8a8: x is a bf16 [M, K] tensor on the GPU")
+    xc, xs = act_quant_fp8(x)
+    return linear_fp8(xc, xs, w_codes, w_scale, out)
+
+
 def linear_any(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor | None = None) -> torch.Tensor:
     """F.linear, or a hand-written kernel: the fp32 one for fp32 operands, the bf16 one-wave-per-SIMD
     kernel (default) or the 8-wave one (all-native mode), when the shape tiles; the skinny kernel for

@@ -8,6 +8,9 @@ The FP8 law, per output row ``w[n, :]``:
     code  = e4m3fn(w / scale), round to nearest even
     dequantised = float(code) * scale
 
+``quantize_act_fp8`` applies the same law to the rows of activations ``x[m, :]`` (one scale per token), for the
+FP8 x FP8 product of more than 64 rows (``ops/csrc/gemm_fp8.hip``).
+
 It is deliberately not the KV cache's ``amax / 448``.  A code has 4 significant bits and the scale is a power of
 two, so the dequantised weight is exactly representable in bf16: a quantised model is an ordinary bf16 model
 whose weights lie on that grid, and every path that reads the parameters (prefill, training kernels, the
@@ -40,11 +43,8 @@ FORMATS = {"fp8": torch.float8_e4m3fn, "mxfp4": torch.uint8}      # format name 
 _E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
 
 
-def quantize_weight_fp8(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
-    """``w [N, K]`` -> (codes float8_e4m3fn [N, K], scale fp32 [N]) by the law above."""
-    if w.dim() != 2:
-        raise ValueError(f"quantize_weight_fp8 takes a [N, K] weight, got {tuple(w.shape)}")
-    wf = w.detach().float()
+def _quantize_rows_fp8(wf: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """The FP8 law on the rows of an fp32 ``[R, K]``: weights (a row per output feature) and activations alike."""
     amax = wf.abs().amax(1)
     # amax = m * 2^e with m in [0.5, 1) and 448 = 0.875 * 2^9: amax / 2^k <= 448 from k = e - 9 on when
     # m <= 0.875, from e - 8 on otherwise.  No division, no logarithm: exact at amax = 448 * 2^k.
@@ -55,6 +55,22 @@ def quantize_weight_fp8(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     # the division by a power of two is exact (up to fp32 underflow, far below the smallest code)
     codes = torch.ldexp(wf, -k[:, None]).to(torch.float8_e4m3fn)
     return codes, scale
+
+
+def quantize_weight_fp8(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """``w [N, K]`` -> (codes float8_e4m3fn [N, K], scale fp32 [N]) by the law above."""
+    if w.dim() != 2:
+        raise ValueError(f"quantize_weight_fp8 takes a [N, K] weight, got {tuple(w.shape)}")
+    return _quantize_rows_fp8(w.detach().float())
+
+
+def quantize_act_fp8(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """``x [M, K]`` -> (codes float8_e4m3fn [M, K], scale fp32 [M]): the weight law applied to the rows of
+    activations (bf16 values read as fp32).  ``dequantize_weight`` is its inverse.  Finite inputs are the contract:
+    the result for a row that holds a NaN or an inf is unspecified."""
+    if x.dim() != 2:
+        raise ValueError(f"quantize_act_fp8 takes [M, K] activations, got {tuple(x.shape)}")
+    return _quantize_rows_fp8(x.detach().float())
 
 
 def dequantize_weight(codes: torch.Tensor, scale: torch.Tensor, dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:

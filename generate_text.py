@@ -45,6 +45,9 @@ def main(argv=None):
                     help="auto: the cache in the model's dtype; fp8: e4m3fn codes with per-row scales")
     ap.add_argument("--weight-dtype", default="auto", choices=("auto", "fp8", "mxfp4"),
                     help="fp8 / mxfp4: the decode steps stream FP8 or MXFP4 codes of the projections (quantize_weights_)")
+    ap.add_argument("--act-dtype", default="auto", choices=("auto", "fp8"),
+                    help="fp8 (with --weight-dtype fp8): products of more than 64 rows -- the prompt -- quantise their "
+                         "activations per token and run on the FP8 GEMM (set_fp8_activations)")
     ap.add_argument("--skinny-gemm", action="store_true",
                     help="bf16 products of at most 64 rows on the weight-streaming kernel (GPU)")
     ap.add_argument("--prefill-chunk", type=int, default=None,
@@ -57,6 +60,8 @@ def main(argv=None):
     model = build_model(args.model_name, impl=args.impl, dtype=dtype, device=dev, seed=args.seed).eval()
     if args.weight_dtype != "auto":
         model.quantize_weights_(args.weight_dtype)
+    if args.act_dtype == "fp8":
+        model.set_fp8_activations(True)
     if args.skinny_gemm:
         from distributed_training_and_deepspeed_amd.ops import gemm
         gemm.set_skinny(True)

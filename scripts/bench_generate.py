@@ -61,6 +61,41 @@ def recompute(model, ids, first, steps):
     return cur
 
 
+@torch.no_grad()
+def prompt_pass(model, args, iters=10):
+    """ms per ``prefill`` of ``--prompt-pass`` tokens: two repeats of ``iters`` calls per arm, the arms alternating."""
+    from distributed_training_and_deepspeed_amd.ops.kv_cache import KVCache
+    S0 = args.prompt_pass
+    arms = {"bf16_act": False, "fp8_act": True} if args.act_dtype == "fp8" else {"bf16_act": False}
+    for B in (int(b) for b in args.batches.split(",")):
+        ids = torch.randint(3, model.cfg.vocab_size, (B, S0), generator=torch.Generator().manual_seed(B)).cuda()
+        cache = KVCache.allocate(model.cfg, B, S0, "cuda", torch.bfloat16)
+
+        def run(on, n):
+            if args.act_dtype == "fp8":
+                model.set_fp8_activations(on)
+            for _ in range(n):
+                cache.reset()
+                logits = model.prefill(ids, cache)
+            return logits
+
+        logits = {k: run(on, 2).float() for k, on in arms.items()}      # warm-up of both arms
+        runs = {k: [] for k in arms}
+        for _ in range(2):
+            for k, on in arms.items():
+                runs[k].append(wall(lambda: run(on, iters))[1] / iters * 1e3)
+        rec = {"case": "prompt_pass", "model": model.cfg.name, "B": B, "prompt": S0, "weight_dtype": args.weight_dtype,
+               "iters": iters}
+        for k, r in runs.items():
+            rec[f"{k}_ms"] = round(sum(r) / 2, 3)
+            rec[f"{k}_runs_ms"] = [round(v, 3) for v in r]
+        if "fp8_act" in runs:
+            rec["fp8_act_speedup"] = round(sum(runs["bf16_act"]) / sum(runs["fp8_act"]), 3)
+            rec["max_abs_logit_diff"] = float((logits["fp8_act"] - logits["bf16_act"]).abs().max())
+            rec["max_abs_logit"] = float(logits["bf16_act"].abs().max())
+        emit(args.out, rec)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", type=str, default="")
@@ -69,6 +104,11 @@ def main():
     ap.add_argument("--kv-cache-dtype", default="auto", choices=("auto", "fp8"), help="auto: the model's dtype")
     ap.add_argument("--weight-dtype", default="auto", choices=("auto", "fp8", "mxfp4"),
                     help="fp8 / mxfp4: quantize_weights_ -- the decode steps stream FP8 or MXFP4 codes of the projections")
+    ap.add_argument("--act-dtype", default="auto", choices=("auto", "fp8"),
+                    help="fp8 (with --weight-dtype fp8): set_fp8_activations -- products of more than 64 rows on the FP8 GEMM")
+    ap.add_argument("--prompt-pass", type=int, default=0, metavar="S0",
+                    help="time the prompt pass alone (prefill of S0 tokens) instead of the decode steps; with --act-dtype fp8 "
+                         "the arms with and without FP8 activations alternate in one process")
     ap.add_argument("--skinny-gemm", action="store_true", help="bf16 products of at most 64 rows on gemm_skinny.hip")
     ap.add_argument("--skip-recompute", action="store_true", help="leave the no-cache baseline out")
     args = ap.parse_args()
@@ -81,6 +121,13 @@ def main():
         if args.weight_dtype != "auto":
             model.quantize_weights_(args.weight_dtype)
         G.set_skinny(args.skinny_gemm)
+        if args.prompt_pass:
+            prompt_pass(model, args)
+            del model
+            torch.cuda.empty_cache()
+            continue
+        if args.act_dtype == "fp8":
+            model.set_fp8_activations(True)
         for B in (int(b) for b in args.batches.split(",")):
             g = torch.Generator().manual_seed(B)
             ids = torch.randint(3, model.cfg.vocab_size, (B, PROMPT + NEW), generator=g).cuda()
