@@ -283,6 +283,8 @@ class CausalLM(nn.Module):
     def _extend_hidden(self, tokens, cache):
         """``extend`` up to the last layer's output ``[B, T, h]``."""
         B, T = tokens.shape
+        if cache.ring:
+            raise NotImplementedError("extend on a ring KV cache is not implemented (one token per step: decode_step)")
         if cache.filled == 0:      # (what generation supports was checked by the prefill that filled it)
             raise ValueError("extend needs a prefilled cache (an empty one takes prefill)")
         if B != cache.batch or T == 0 or cache.filled + T > cache.max_len:
@@ -305,7 +307,7 @@ class CausalLM(nn.Module):
                  do_sample: bool = False, temperature: float = 1.0, top_k: int = 0, eos_token_id: int | None = None,
                  seed: int = 0, max_len: int | None = None, graph: bool = False,
                  logits_out: list | None = None, kv_dtype=None, cache_out: list | None = None,
-                 prefill_chunk: int | None = None) -> torch.Tensor:
+                 prefill_chunk: int | None = None, kv_ring: bool = False) -> torch.Tensor:
         """``input_ids [B, S0]`` continued by ``max_new_tokens`` = N tokens: int64 ``[B, S0 + N]``.  Greedy by
         default; ``do_sample``: temperature, then top-k (0 = the whole vocabulary), drawn with a
         ``torch.Generator`` seeded with ``seed``.  ``attention_mask``: a LEFT-padded batch (``prefill``).  After
@@ -329,6 +331,11 @@ class CausalLM(nn.Module):
         keys and values as quantised, where the one-piece prefill attends the unquantised projection, so the two
         differ by the quantisation error.  None: the prompt in one piece.
 
+        ``kv_ring=True`` (a model with a sliding window W, else a ``ValueError``): the cache is a ring of W slots
+        rounded up to 64 (``KVCache.allocate(ring=True)``) instead of ``max_len`` -- the same keys attended, so the
+        same logits up to summation order; memory and the time of a step no longer grow with the position.  The
+        prompt may be longer than the ring; ``prefill_chunk`` with it is a ``ValueError`` (no multi-token ring step).
+
         After ``quantize_weights_("fp8")`` and ``set_fp8_activations(True)`` the prompt pass (and every chunk of
         more than 64 rows) runs its projections on the FP8 GEMM with activations quantised per token: its logits
         differ from the weight-only model's by that quantisation; the decode steps of at most 64 sequences do not
@@ -346,7 +353,9 @@ class CausalLM(nn.Module):
         input_ids = input_ids.to(dev)
         if attention_mask is not None:
             attention_mask = attention_mask.to(dev)
-        cache = KVCache.allocate(self.cfg, B, max_len, dev, w.dtype, kv_dtype=kv_dtype)
+        if kv_ring and prefill_chunk is not None:
+            raise ValueError("generate: prefill_chunk needs the linear cache (kv_ring=False)")
+        cache = KVCache.allocate(self.cfg, B, max_len, dev, w.dtype, kv_dtype=kv_dtype, ring=bool(kv_ring))
         if cache_out is not None:
             cache_out.append(cache)
         gen = torch.Generator(device=dev).manual_seed(seed) if do_sample else None

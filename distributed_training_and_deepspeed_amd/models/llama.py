@@ -164,18 +164,21 @@ class LlamaLayer(nn.Module):
         else:
             qkv = self._proj_ref(ref_rms_norm(x2d, self.n1_g, eps), "qkv_w")
         ks, vs = cache.layer_scales(i)      # (None, None) unless the cache is FP8
+        ring = cache.ring    # (slot = position mod cache.slots; a prompt longer than the ring keeps its last rows)
+        if ring and not prefill and Sq != 1:
+            raise NotImplementedError("several tokens per step (extend, chunked prefill) on a ring KV cache")
         Fx.rope_append_(qkv, table, kc, vc, cache.kv_len, B, Sq, H, D, kv_heads=Hkv, overflow=cache.overflow,
-                        k_scale=ks, v_scale=vs)
-        if prefill:      # (also with an FP8 cache: the prompt attends its own unquantised k / v)
+                        k_scale=ks, v_scale=vs, ring=ring)
+        if prefill:      # (also with an FP8 or a ring cache: the prompt attends its own unquantised k / v)
             attn = A.attn_fwd if fused else A.attn_fwd_ref
             actx = attn(qkv, B, Sq, H, D, c.causal, key_range=key_range, kv_heads=Hkv if Hkv != H else None,
                         window=window)[0]
         elif fused and Sq == 1:
             actx, _ = A.attn_decode(qkv, kc, vc, cache.kv_next, B, H, D, Hkv, window, cache.kv_start,
-                                    splits=cache.splits, workspace=cache.workspace, k_scale=ks, v_scale=vs)
+                                    splits=cache.splits, workspace=cache.workspace, k_scale=ks, v_scale=vs, ring=ring)
         elif Sq == 1:
             actx, _ = A.attn_decode_ref(qkv, kc, vc, cache.kv_next, B, H, D, Hkv, window, cache.kv_start,
-                                        k_scale=ks, v_scale=vs)
+                                        k_scale=ks, v_scale=vs, ring=ring)
         elif fused:
             splits, ws = cache.extend_workspace(Sq)
             actx, _ = A.attn_extend(qkv, kc, vc, cache.kv_len, B, Sq, H, D, Hkv, window, cache.kv_start,

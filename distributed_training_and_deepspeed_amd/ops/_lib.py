@@ -111,6 +111,11 @@ _SIGS = {
     # (the _fp8 forms, e4m3 codes with per-row fp32 scales: k_scale, v_scale behind the caches; bf16 only, no dtype)
     "dtd_attn_decode_fp8": (I, [P, L, P, P, P, P, P, P, P, L, P, P, L, I, I, I, I, I, I, F, I, P]),
     "dtd_rope_append_fp8": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, L, I, I, P]),
+    # attention_ring.hip (the four above on the ring cache: the same arguments, the ring's slots R for Smax)
+    "dtd_attn_decode_ring": (I, [P, L, P, P, P, P, P, L, P, P, L, I, I, I, I, I, I, F, I, P]),
+    "dtd_rope_append_ring": (I, [I, P, P, P, P, P, P, I, I, I, I, I, L, I, I, P]),
+    "dtd_attn_decode_ring_fp8": (I, [P, L, P, P, P, P, P, P, P, L, P, P, L, I, I, I, I, I, I, F, I, P]),
+    "dtd_rope_append_ring_fp8": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, L, I, I, P]),
     # attention_extend.hip (dtd_attn_decode's arguments with T behind B; the _fp8 form likewise)
     "dtd_attn_extend": (I, [P, L, P, P, P, P, P, L, P, P, L, I, I, I, I, I, I, I, F, I, P]),
     "dtd_attn_extend_fp8": (I, [P, L, P, P, P, P, P, P, P, L, P, P, L, I, I, I, I, I, I, I, F, I, P]),

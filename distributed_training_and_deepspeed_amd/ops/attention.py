@@ -736,6 +736,24 @@ def _decode_window(window) -> int:
     return int(window)
 
 
+def _ring_outside(kv_len, kv_start, window: int, R: int):
+    """bool [B, R] of a decode call on a ring cache of R slots (ops/kv_cache.py): whether slot u takes no part.
+    With hi = kv_len (not clamped: the ring has no last position) and lo = max(kv_start, 0, hi - W, hi - R), slot u
+    holds the position (hi - 1) - ((hi - 1 - u) mod R) and takes part iff that is >= lo."""
+    hi = kv_len.to(torch.int64)
+    lo = torch.zeros_like(hi) if kv_start is None else kv_start.to(device=hi.device, dtype=torch.int64).clamp(min=0)
+    lo = torch.maximum(lo, hi - min(window, R)).view(-1, 1)
+    last = (hi - 1).view(-1, 1)
+    u = torch.arange(R, device=hi.device).view(1, R)
+    return last - torch.remainder(last - u, R) < lo
+
+
+def _check_ring(window: int, R: int) -> None:
+    if not window or R < window or R % DECODE_KEY_TILE:
+        raise ValueError(f"a ring cache needs a window and R >= window, R a multiple of {DECODE_KEY_TILE}: got window = "
+                         f"{window or None}, R = {R}")
+
+
 _FP8 = torch.float8_e4m3fn
 
 
@@ -768,16 +786,19 @@ def _check_decode(qkv, k_cache, v_cache, kv_len, B, H, Hkv, D, k_scale=None, v_s
 
 
 def attn_decode_ref(qkv, k_cache, v_cache, kv_len, B, H, D, kv_heads=None, window=None, kv_start=None, scale=None,
-                    k_scale=None, v_scale=None):
+                    k_scale=None, v_scale=None, ring: bool = False):
     """Math reference of ``attn_decode``: plain PyTorch over the whole cache with the slots outside
     [lo, hi) masked, softmax in fp32 (fp64 for fp64 inputs), the rounding points of ``attn_fwd_ref``
     (ctx rounded once, at the end).  An FP8 cache (``k_scale`` / ``v_scale``) is dequantised first --
-    ``float(code) * scale`` in the compute dtype -- and then takes the same math.
+    ``float(code) * scale`` in the compute dtype -- and then takes the same math.  ``ring``: the caches are rings
+    of R = ``k_cache.shape[2]`` slots and the mask is ``_ring_outside``'s.
     Returns (ctx [B, H*D], lse [B, H] fp32)."""
     Hkv = _kv_heads(kv_heads, H)
     fp8 = _check_decode(qkv, k_cache, v_cache, kv_len, B, H, Hkv, D, k_scale, v_scale)
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     Smax = k_cache.shape[2]
+    if ring:
+        _check_ring(_decode_window(window), Smax)
     c = _cdt(qkv)
     q = qkv[:, :H * D].reshape(B, H, 1, D).to(c)
     G = H // Hkv
@@ -785,9 +806,13 @@ def attn_decode_ref(qkv, k_cache, v_cache, kv_len, B, H, D, kv_heads=None, windo
         k_cache, v_cache = k_cache.to(c) * k_scale.to(c).unsqueeze(-1), v_cache.to(c) * v_scale.to(c).unsqueeze(-1)
     k, v = k_cache.to(c).repeat_interleave(G, 1), v_cache.to(c).repeat_interleave(G, 1)     # [B, H, Smax, D]
     s = torch.matmul(q, k.transpose(-1, -2)) * scale                                       # [B, H, 1, Smax]
-    lo, hi = _decode_bounds(kv_len.to(qkv.device), kv_start, _decode_window(window), Smax)
-    j = torch.arange(Smax, device=qkv.device).view(1, Smax)
-    outside = ((j < lo.view(B, 1)) | (j >= hi.view(B, 1))).view(B, 1, 1, Smax)
+    if ring:
+        outside = _ring_outside(kv_len.to(qkv.device).reshape(B), kv_start, _decode_window(window), Smax)
+    else:
+        lo, hi = _decode_bounds(kv_len.to(qkv.device), kv_start, _decode_window(window), Smax)
+        j = torch.arange(Smax, device=qkv.device).view(1, Smax)
+        outside = (j < lo.view(B, 1)) | (j >= hi.view(B, 1))
+    outside = outside.view(B, 1, 1, Smax)
     s = s.masked_fill(outside, float("-inf"))
     lse = torch.logsumexp(s, -1)
     prob = _probs(s, lse)
@@ -804,7 +829,7 @@ def decode_kernel_supported(qkv: torch.Tensor, H: int, Hkv: int, D: int) -> bool
 
 def attn_decode(qkv, k_cache, v_cache, kv_len, B, H, D, kv_heads=None, window=None, kv_start=None, splits=None,
                 workspace: torch.Tensor | None = None, out: tuple | None = None, k_scale: torch.Tensor | None = None,
-                v_scale: torch.Tensor | None = None):
+                v_scale: torch.Tensor | None = None, ring: bool = False):
     """Attention of one new token per sequence against the cache: ``qkv [B, (H + 2*Hkv)*D]`` is the step's
     packed projection output (only its q block is read; its k / v rows are already in the cache,
     ``functional.rope_append_``), ``k_cache`` / ``v_cache [B, Hkv, Smax, D]``, ``kv_len`` / ``kv_start``
@@ -817,20 +842,27 @@ def attn_decode(qkv, k_cache, v_cache, kv_len, B, H, D, kv_heads=None, window=No
     shape or dtype, are a ``ValueError``.  ``splits``: override of ``decode_splits`` (tests, benchmarks).  ``workspace``: fp32 buffer of
     at least ``decode_workspace_floats`` elements (``KVCache`` holds one, so a captured step allocates
     nothing for it); allocated here when None.  ``out``: (ctx, lse) tensors to write, of the returned
-    shapes and dtypes, ctx with unit column stride."""
+    shapes and dtypes, ctx with unit column stride.
+
+    ``ring=True``: the caches are rings ``[B, Hkv, R, D]`` (scales ``[B, Hkv, R]``) in which position j lives in slot
+    j mod R, ``kv_len`` / ``kv_start`` staying absolute positions (``_ring_outside``); the same routing rule, on the
+    ring kernel (ops/csrc/attention_ring.hip), whose splits are ``decode_splits(B, Hkv, R)``.  A ring needs a
+    window, R >= window and R a multiple of ``DECODE_KEY_TILE``: anything else is a ``ValueError``."""
     Hkv = _kv_heads(kv_heads, H)
     window = _decode_window(window)
     fp8 = _check_decode(qkv, k_cache, v_cache, kv_len, B, H, Hkv, D, k_scale, v_scale)
+    if ring:
+        _check_ring(window, k_cache.shape[2])
     if not decode_kernel_supported(qkv, H, Hkv, D):
         ctx, lse = attn_decode_ref(qkv, k_cache, v_cache, kv_len, B, H, D, Hkv, window, kv_start, k_scale=k_scale,
-                                   v_scale=v_scale)
+                                   v_scale=v_scale, ring=ring)
         if out is not None:
             out[0].copy_(ctx)
             out[1].copy_(lse)
             return out[0], out[1]
         return ctx, lse
-    entry = "dtd_attn_decode_fp8" if fp8 else "dtd_attn_decode"
-    _require(entry, "FP8 decode" if fp8 else "decode")
+    entry = ("dtd_attn_decode_ring" if ring else "dtd_attn_decode") + ("_fp8" if fp8 else "")
+    _require(entry, ("FP8 " if fp8 else "") + ("ring decode" if ring else "decode"))
     Smax = k_cache.shape[2]
     if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
         raise ValueError("k_cache / v_cache must be contiguous [B, Hkv, Smax, D]")

@@ -491,7 +491,7 @@ def rope_(qkv: torch.Tensor, table: torch.Tensor, B: int, S: int, H: int, D: int
 def rope_append_(qkv: torch.Tensor, table: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
                  kv_len: torch.Tensor, B: int, Sq: int, H: int, D: int, kv_heads: int | None = None,
                  overflow: torch.Tensor | None = None, k_scale: torch.Tensor | None = None,
-                 v_scale: torch.Tensor | None = None) -> torch.Tensor:
+                 v_scale: torch.Tensor | None = None, ring: bool = False) -> torch.Tensor:
     """``rope_`` with ``pos = kv_len[b] + s`` IN PLACE on the packed ``qkv [B*Sq, (H + 2*Hkv)*D]`` (bitwise
     the same rotation), plus the KV-cache append: the rotated k row and the v row of token (b, s) go to
     slot ``kv_len[b] + s`` of ``k_cache`` / ``v_cache [B, Hkv, Smax, D]``.  ``kv_len``: device int32 [B],
@@ -502,7 +502,12 @@ def rope_append_(qkv: torch.Tensor, table: torch.Tensor, k_cache: torch.Tensor, 
     rotated exactly as above and each row is quantised by ``ops.kv_cache.quantize_kv_ref``'s law -- D codes and
     one scale per slot, neither written for a row that does not fit.  bf16 on the GPU with D 64 / 128 runs the
     quantising kernel (same codes and scales, bit for bit); everything else -- the CPU, fp32 activations,
-    another D -- the PyTorch reference."""
+    another D -- the PyTorch reference.
+
+    ``ring=True``: the caches are rings of R = ``k_cache.shape[2]`` slots (ops/kv_cache.py) and position p lives in
+    slot ``p mod R``.  Every row is rotated as above; only the last R rows of the call (s >= Sq - R) are stored,
+    so no slot is written twice; a position outside [0, table positions) stores nothing and sets ``overflow``.
+    The same routing, on the ring kernels (ops/csrc/attention_ring.hip)."""
     fp8 = k_cache.dtype == torch.float8_e4m3fn or v_cache.dtype == torch.float8_e4m3fn or k_scale is not None \
         or v_scale is not None
     Hkv = H if kv_heads is None else int(kv_heads)
@@ -532,9 +537,10 @@ def rope_append_(qkv: torch.Tensor, table: torch.Tensor, k_cache: torch.Tensor, 
     # the kernels' domains: the plain append takes both kernel dtypes and any D % 16; the quantising one bf16, D 64 / 128
     kernel = (qkv.is_cuda and qkv.dtype == torch.bfloat16 and D in (64, 128)) if fp8 else (_kernel_dtype(qkv) and D % 16 == 0)
     if kernel and qkv.stride(0) % 8 == 0 and qkv.data_ptr() % 16 == 0:
-        entry = "dtd_rope_append_fp8" if fp8 else "dtd_rope_append"
+        entry = ("dtd_rope_append_ring" if ring else "dtd_rope_append") + ("_fp8" if fp8 else "")
         if not _lib.has(entry):
-            raise _lib.KernelError(f"the kernel library has no {'FP8 ' if fp8 else ''}KV-cache append entry point (stale build)")
+            raise _lib.KernelError(f"the kernel library has no {'FP8 ' if fp8 else ''}KV-cache {'ring ' if ring else ''}append "
+                                   "entry point (stale build)")
         table = table.contiguous()
         kv32 = kv_len.reshape(-1).to(device=qkv.device, dtype=torch.int32).contiguous()
         head = (qkv.data_ptr(), table.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr())
@@ -551,17 +557,34 @@ def rope_append_(qkv: torch.Tensor, table: torch.Tensor, k_cache: torch.Tensor, 
         (kq, ks), (vq, vs) = (quantize_kv_ref(new) for _, new in pairs)
         pairs = ((k_cache.view(torch.uint8), kq.view(torch.uint8)), (k_scale.unsqueeze(-1), ks.unsqueeze(-1)),
                  (v_cache.view(torch.uint8), vq.view(torch.uint8)), (v_scale.unsqueeze(-1), vs.unsqueeze(-1)))
-    _append_rows_ref(slot, overflow, pairs)
+    _append_rows_ref(slot, overflow, pairs, table.shape[0] if ring else None)
     return qkv
 
 
-def _append_rows_ref(slot: torch.Tensor, overflow: torch.Tensor, pairs) -> None:
+def _append_rows_ref(slot: torch.Tensor, overflow: torch.Tensor, pairs, ring_max_pos: int | None = None) -> None:
     """The append of ``rope_append_``'s PyTorch branch: for every (cache ``[B, Hkv, Smax, W]``, new
     ``[B, Sq, Hkv, W]``) of ``pairs``, row (b, s) of new into slot ``slot[b, s]`` of cache; a slot outside
-    [0, Smax) is not written and raises ``overflow``."""
+    [0, Smax) is not written and raises ``overflow``.
+
+    ``ring_max_pos`` (a ring cache of R = Smax slots): ``slot`` holds positions; the last min(Sq, R) rows go to
+    ``position mod R`` -- distinct slots -- and a position outside [0, ring_max_pos) keeps the slot's content and
+    raises ``overflow``."""
     B, Sq = slot.shape
     dev = slot.device
     Hkv, Smax = pairs[0][0].shape[1:3]
+    if ring_max_pos is not None:
+        valid = (slot >= 0) & (slot < ring_max_pos)
+        overflow.copy_(torch.maximum(overflow, (~valid).any().to(overflow.dtype).reshape(overflow.shape)))
+        s0 = max(0, Sq - Smax)
+        keep = valid[:, s0:].view(B, 1, Sq - s0, 1)
+        rows = ((torch.arange(B, device=dev).view(B, 1, 1) * Hkv + torch.arange(Hkv, device=dev).view(1, Hkv, 1)) * Smax
+                + torch.remainder(slot[:, s0:], Smax).view(B, 1, Sq - s0)).reshape(-1)
+        for cache, new in pairs:
+            W = cache.shape[3]
+            flat = cache.view(B * Hkv * Smax, W)
+            val = torch.where(keep, new[:, s0:].transpose(1, 2), flat[rows].view(B, Hkv, Sq - s0, W))
+            flat.index_copy_(0, rows, val.reshape(-1, W))
+        return
     fits = (slot >= 0) & (slot < Smax)
     overflow.copy_(torch.maximum(overflow, (~fits).any().to(overflow.dtype).reshape(overflow.shape)))
     # index_copy_ with the slots clamped into the cache.  A row that does not fit lands on slot 0 or

@@ -2,8 +2,9 @@
 
 Per layer one K and one V tensor ``[B, Hkv, Smax, D]`` in the model's dtype: the keys of one (sequence,
 key/value head) are one contiguous stream, which is what the decode kernel reads
-(ops/csrc/attention_decode.hip).  The cache is linear -- a sliding window is a bound inside the kernel,
-not a ring buffer.  Its position lives in device memory and is shared by all layers:
+(ops/csrc/attention_decode.hip).  By default the cache is linear -- slot = position, a sliding window being
+a bound inside the kernel; the ring layout below is opt-in.  Its position lives in device memory and is
+shared by all layers:
 
 * ``kv_len``   int32 [B]: slots written;
 * ``kv_next``  int32 [B]: ``kv_len + 1``, what a decode step's attention takes as its length (the new token
@@ -23,6 +24,22 @@ fp32, x the row as the bf16 cache would hold it (the rotated k as rounded to the
 ``scale = amax / 448`` (1 when amax is 0); ``code = e4m3fn(x / scale)``, both IEEE fp32 divisions, the conversion
 round-to-nearest-even; the dequantised value is ``float(code) * scale``.  The quantising append kernel writes the
 same codes and scales bit for bit.  Half the bytes of a bf16 cache plus 4 / D of them again for the scales.
+
+Ring cache (``ring=True``, opt-in, sliding-window models; ops/csrc/attention_ring.hip): K / V are ``[L, B, Hkv, R,
+D]`` (scales ``[L, B, Hkv, R]``) and position j of a sequence lives in slot ``j mod R``.  R, ``cache.slots``, is a
+multiple of the decode kernel's 64-key tile and at least the window W (default: W rounded up to the tile).  The
+counters above stay ABSOLUTE positions -- they are the rotary positions too -- and advance as in the linear cache;
+``max_len`` stays the bound on positions.  One law for the kernels and the PyTorch reference:
+
+* append of Sq rows at the positions ``p = kv_len[b] + s``: every q and k row is rotated; row s is stored in slot
+  ``p mod R`` only if it is among the last R rows of the call (no slot is written twice); a position outside
+  [0, rotary table) stores nothing and raises ``overflow``;
+* decode with ``hi = kv_len[b]`` (the new token counted) attends ``lo <= j < hi``, ``lo = max(kv_start[b], 0, hi - W,
+  hi - R)``: slot u holds the position ``(hi - 1) - ((hi - 1 - u) mod R)`` and takes part iff that is ``>= lo``.
+
+The cache's bytes, the decode kernel's splits and its workspace follow R, not the number of positions: memory
+and the time of a step stop growing once a sequence is longer than the window.  Multi-token steps on a ring
+(``attn_extend``, chunked prefill) are not implemented; ``ring_slots`` leaves room for them (R >= W + T - 1).
 """
 from __future__ import annotations
 
@@ -62,42 +79,60 @@ def _kv_dtype(kv_dtype, dtype):
 
 class KVCache:
     def __init__(self, k, v, kv_len, kv_next, kv_start, overflow, workspace, splits, k_scale=None, v_scale=None,
-                 num_heads=None):
-        self.k, self.v = k, v                      # [L, B, Hkv, Smax, D]
+                 num_heads=None, ring=False, max_len=None):
+        self.k, self.v = k, v                      # [L, B, Hkv, Smax, D] (a ring: [L, B, Hkv, R, D])
         self.k_scale, self.v_scale = k_scale, v_scale      # FP8 cache: fp32 [L, B, Hkv, Smax]; else None
         self.kv_len, self.kv_next, self.kv_start, self.overflow = kv_len, kv_next, kv_start, overflow
         self.filled = 0                            # host mirror of kv_len (every sequence advances alike)
         self.workspace, self.splits = workspace, splits
         self._extend_ws, self._extend_t = None, 0  # the extend kernel's split workspace: see extend_workspace
-        self.num_layers, self.batch, self.kv_heads, self.max_len, self.head_dim = k.shape
+        self.num_layers, self.batch, self.kv_heads, self.slots, self.head_dim = k.shape
+        self.ring = bool(ring)                     # position j in slot j mod slots
+        self.max_len = self.slots if max_len is None else max_len     # the bound on positions
         self.num_heads = num_heads or self.kv_heads        # query heads (the extend workspace's size)
 
     @classmethod
-    def allocate(cls, cfg, batch: int, max_len: int, device, dtype, kv_dtype=None) -> "KVCache":
+    def allocate(cls, cfg, batch: int, max_len: int, device, dtype, kv_dtype=None, ring: bool = False,
+                 ring_slots: int | None = None) -> "KVCache":
         """The cache of ``cfg`` for ``batch`` sequences of up to ``max_len`` positions (prompt and
         continuation), empty.  ``max_len`` beyond ``cfg.max_positions`` is a ``ValueError``: the rotary
         table ends there.  ``kv_dtype``: None or ``dtype`` -- K / V in the model's dtype; ``torch.float8_e4m3fn``
-        or ``"fp8"`` -- the FP8 cache (module docstring); anything else is a ``ValueError``."""
+        or ``"fp8"`` -- the FP8 cache (module docstring); anything else is a ``ValueError``.
+
+        ``ring=True`` (a config with ``sliding_window`` = W, else a ``ValueError``): the ring layout of R slots
+        (module docstring), R = ``ring_slots`` or W rounded up to the key tile; ``ring_slots`` must be a multiple of
+        the tile and at least W (a later chunk of T tokens per step needs W + T - 1).  ``max_len`` still bounds the
+        positions; the bytes, the splits and the workspace follow R."""
         fp8 = _kv_dtype(kv_dtype, dtype) is not None
         if batch <= 0 or max_len <= 0:
             raise ValueError(f"KVCache: batch = {batch} and max_len = {max_len} must be positive")
         if cfg.rope_theta > 0 and max_len > cfg.max_positions:
             raise ValueError(f"KVCache: max_len = {max_len} exceeds max_positions = {cfg.max_positions} (the rotary table)")
         L, Hkv, D = cfg.num_layers, cfg.kv_heads, cfg.head_dim
+        slots = max_len
+        if ring:
+            W, T = cfg.sliding_window or 0, A.DECODE_KEY_TILE
+            if not W:
+                raise ValueError("KVCache: ring=True needs a model with a sliding window")
+            slots = -(-W // T) * T if ring_slots is None else int(ring_slots)
+            if slots < W or slots % T:
+                raise ValueError(f"KVCache: ring_slots = {ring_slots} must be a multiple of {T} and at least the window {W}")
+        elif ring_slots is not None:
+            raise ValueError("KVCache: ring_slots goes with ring=True")
         if fp8:      # (zeros through uint8: code 0 is 0.0)
-            k, v = (torch.zeros((L, batch, Hkv, max_len, D), dtype=torch.uint8, device=device).view(FP8) for _ in range(2))
-            k_scale, v_scale = (torch.ones((L, batch, Hkv, max_len), dtype=torch.float32, device=device) for _ in range(2))
+            k, v = (torch.zeros((L, batch, Hkv, slots, D), dtype=torch.uint8, device=device).view(FP8) for _ in range(2))
+            k_scale, v_scale = (torch.ones((L, batch, Hkv, slots), dtype=torch.float32, device=device) for _ in range(2))
         else:
-            k = torch.zeros((L, batch, Hkv, max_len, D), dtype=dtype, device=device)
+            k = torch.zeros((L, batch, Hkv, slots, D), dtype=dtype, device=device)
             v = torch.zeros_like(k)
             k_scale = v_scale = None
-            assert (k.numel() + v.numel()) * k.element_size() == kv_cache_bytes(cfg, batch, max_len, dtype)
-        splits = A.decode_splits(batch, Hkv, max_len)
+            assert (k.numel() + v.numel()) * k.element_size() == kv_cache_bytes(cfg, batch, slots, dtype)
+        splits = A.decode_splits(batch, Hkv, slots)
         ws = torch.empty(A.decode_workspace_floats(batch, cfg.num_heads, D, splits), dtype=torch.float32, device=device)
         ints = torch.zeros((4, batch), dtype=torch.int32, device=device)
         ints[1].fill_(1)
-        cache = cls(k, v, ints[0], ints[1], ints[2], ints[3, :1], ws, splits, k_scale, v_scale, cfg.num_heads)
-        assert cache.nbytes() == kv_cache_bytes(cfg, batch, max_len, dtype, FP8 if fp8 else None)
+        cache = cls(k, v, ints[0], ints[1], ints[2], ints[3, :1], ws, splits, k_scale, v_scale, cfg.num_heads, ring, max_len)
+        assert cache.nbytes() == kv_cache_bytes(cfg, batch, slots, dtype, FP8 if fp8 else None)
         return cache
 
     @property
@@ -126,6 +161,8 @@ class KVCache:
         allocated on first use, for the largest T seen, and kept (None while no T seen needs one: a single split
         writes its output itself).  A captured step calls this once before the capture, so the capture allocates
         nothing."""
+        if self.ring:
+            raise NotImplementedError("multi-token cached attention (attn_extend) on a ring cache is not implemented")
         H = self.num_heads
         splits = A.extend_splits(self.batch, self.kv_heads, self.max_len, T, H // self.kv_heads)
         if T > self._extend_t:

@@ -2,7 +2,7 @@
 
     python generate_text.py --model-name llama-tiny-gqa --batch-size 4 --prompt-len 64 --max-new-tokens 64 \
         [--graph] [--impl auto|fused|reference] [--sample --top-k 50 --temperature 0.8] [--metrics-json F] \
-        [--kv-cache-dtype auto|fp8]
+        [--kv-cache-dtype auto|fp8] [--kv-ring]
 
 Prints the token ids of row 0, the prefill time and the decode rate.  The prompt goes through the model once
 (``CausalLM.prefill``); every further token costs one ``decode_step`` against the cache, whose attention is the
@@ -43,6 +43,8 @@ def main(argv=None):
     ap.add_argument("--dtype", default=None, choices=("bfloat16", "float32"), help="default: bfloat16 on the GPU")
     ap.add_argument("--kv-cache-dtype", default="auto", choices=("auto", "fp8"),
                     help="auto: the cache in the model's dtype; fp8: e4m3fn codes with per-row scales")
+    ap.add_argument("--kv-ring", action="store_true",
+                    help="sliding-window models: the cache as a ring of window slots (rounded up to 64) instead of max_len")
     ap.add_argument("--weight-dtype", default="auto", choices=("auto", "fp8", "mxfp4"),
                     help="fp8 / mxfp4: the decode steps stream FP8 or MXFP4 codes of the projections (quantize_weights_)")
     ap.add_argument("--act-dtype", default="auto", choices=("auto", "fp8"),
@@ -69,7 +71,8 @@ def main(argv=None):
     B, S0, N = args.batch_size, args.prompt_len, args.max_new_tokens
     ids = torch.randint(3, cfg.vocab_size, (B, S0), generator=torch.Generator().manual_seed(args.seed)).to(dev)
     kw = dict(do_sample=args.sample, temperature=args.temperature, top_k=args.top_k, seed=args.seed, graph=args.graph,
-              kv_dtype=None if args.kv_cache_dtype == "auto" else args.kv_cache_dtype, prefill_chunk=args.prefill_chunk)
+              kv_dtype=None if args.kv_cache_dtype == "auto" else args.kv_cache_dtype, prefill_chunk=args.prefill_chunk,
+              kv_ring=args.kv_ring)
 
     def timed(n):
         _sync(dev)
@@ -85,7 +88,7 @@ def main(argv=None):
     rate = B * max(N - 1, 0) / decode_s
     print("tokens[0]:", out[0].tolist())
     print(f"{cfg.name}: batch {B}, prompt {S0}, {N} new tokens, {dtype}, impl {args.impl}"
-          f"{', fp8 kv cache' if args.kv_cache_dtype == 'fp8' else ''}"
+          f"{', fp8 kv cache' if args.kv_cache_dtype == 'fp8' else ''}{', ring kv cache' if args.kv_ring else ''}"
           f"{', graph' if args.graph and dev.type == 'cuda' else ''}")
     print(f"prefill {t_prefill * 1e3:.2f} ms, decode {rate:.1f} tokens/s ({decode_s / max(N - 1, 1) * 1e3:.3f} ms/step)")
     if args.metrics_json:

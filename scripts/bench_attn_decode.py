@@ -21,7 +21,13 @@ per row, ops/kv_cache.py) against the bf16 kernel on the bf16 cache of the same 
 two repeats each.  One JSON line per shape: microseconds and TB/s of valid bytes (the FP8 arm's include its scales);
 ``fp8_faster`` marks a gain beyond the bf16 arm's own difference between its repeats.
 
+``--ring`` is a third arm, on the windowed model only (Mistral: B in {1, 8, 64}, 4096 / 8192 / 32768 positions, W =
+R = 4096): the ring kernel (ops/csrc/attention_ring.hip) on a cache of R slots against the linear kernel on the
+linear cache that holds the same keys, alternating, two repeats each.  One JSON line per shape: microseconds, the
+splits and the cache bytes of each; ``ring_slower`` marks a shape where the ring loses by more than the spread.
+
 Usage: python scripts/bench_attn_decode.py [--iters K] [--budget-s SECONDS] [--out profiles/attn_decode.jsonl]
+       python scripts/bench_attn_decode.py --ring [--iters K] [--out profiles/attn_decode_ring.jsonl]
        python scripts/bench_attn_decode.py --fp8 [--iters K] [--out profiles/attn_decode_fp8.jsonl]
 """
 from __future__ import annotations
@@ -153,6 +159,59 @@ def fp8_arm(args):
                 torch.cuda.empty_cache()
 
 
+def ring_arm(args):
+    """The ring kernel on a cache of R = W slots against the linear kernel on the linear cache of the same keys, for
+    the windowed model of the table: position j of the linear cache sits in slot j mod R of the ring, so both attend
+    the same W keys.  The two alternate, two repeats each; the spread is the larger difference between repeats."""
+    dev, dt = "cuda", torch.bfloat16
+    torch.manual_seed(0)
+    for name, H, Hkv, D, W, extra in MODELS:
+        if not W:
+            continue
+        R = W
+        for B in BATCHES:
+            for n in (4096, 8192) + extra:
+                qkv = torch.randn(B, (H + 2 * Hkv) * D, device=dev, dtype=dt)
+                k = torch.randn(B, Hkv, n, D, device=dev, dtype=dt)
+                v = torch.randn(B, Hkv, n, D, device=dev, dtype=dt)
+                slot = torch.arange(n - R, n, device=dev) % R
+                kr, vr = torch.empty(B, Hkv, R, D, device=dev, dtype=dt), torch.empty(B, Hkv, R, D, device=dev, dtype=dt)
+                kr[:, :, slot], vr[:, :, slot] = k[:, :, n - R:], v[:, :, n - R:]
+                kv_len = torch.full((B,), n, dtype=torch.int32, device=dev)
+                splits = {"linear": A.decode_splits(B, Hkv, n), "ring": A.decode_splits(B, Hkv, R)}
+                ws = torch.empty(A.decode_workspace_floats(B, H, D, max(splits.values())), dtype=torch.float32, device=dev)
+                out = (torch.empty(B, H * D, device=dev, dtype=dt), torch.empty(B, H, device=dev, dtype=torch.float32))
+                outr = (torch.empty_like(out[0]), torch.empty_like(out[1]))
+
+                def linear():
+                    return A.attn_decode(qkv, k, v, kv_len, B, H, D, Hkv, W, splits=splits["linear"], workspace=ws, out=out)
+
+                def ring():
+                    return A.attn_decode(qkv, kr, vr, kv_len, B, H, D, Hkv, W, splits=splits["ring"], workspace=ws, out=outr,
+                                         ring=True)
+
+                diff = float((linear()[0].float() - ring()[0].float()).abs().max())
+                runs = {"linear": [], "ring": []}
+                for _ in range(2):
+                    for key, fn in (("linear", linear), ("ring", ring)):
+                        runs[key].append(timeit(fn, args.iters))
+                mean = {key: sum(r) / 2 for key, r in runs.items()}
+                spread = max(abs(r[0] - r[1]) for r in runs.values())
+                rec = {"case": "attn_decode_ring", "model": name, "B": B, "H": H, "Hkv": Hkv, "D": D, "positions": n,
+                       "window": W, "ring_slots": R, "iters": args.iters, "max_abs_diff_ring_vs_linear": round(diff, 5)}
+                for key, slots in (("linear", n), ("ring", R)):
+                    rec[f"{key}_splits"] = splits[key]
+                    rec[f"{key}_cache_bytes"] = 2 * B * Hkv * slots * D * 2
+                    rec[f"{key}_us"] = round(mean[key], 1)
+                    rec[f"{key}_runs_us"] = [round(x, 1) for x in runs[key]]
+                rec["ring_over_linear"] = round(mean["ring"] / mean["linear"], 3)
+                rec["spread_us"] = round(spread, 1)
+                rec["ring_slower"] = bool(mean["ring"] - mean["linear"] > spread)
+                emit(args.out, rec)
+                del qkv, k, v, kr, vr, ws
+                torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
@@ -160,11 +219,15 @@ def main():
     ap.add_argument("--out", type=str, default="")
     ap.add_argument("--fp8", action="store_true", help="the FP8 arm: the FP8 cache's kernel against the bf16 kernel "
                                                        "(profiles/attn_decode_fp8.jsonl)")
+    ap.add_argument("--ring", action="store_true", help="the ring arm: the ring cache's kernel against the linear one "
+                                                        "on the windowed shapes (profiles/attn_decode_ring.jsonl)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_attn_decode.py needs a GPU")
     if args.fp8:
         return fp8_arm(args)
+    if args.ring:
+        return ring_arm(args)
     dev, dt = "cuda", torch.bfloat16
     native = sdpa_native_gqa(dev)
     t_start = time.perf_counter()
