@@ -47,6 +47,7 @@ from .config import BLOOM_560M, TransformerConfig, get_config
 from .layers import Embeddings, LayerNorm, LMHead, RMSNorm
 from .llama import LlamaLayer
 from .moe import MoeLlamaLayer
+from ..ops.functional import sample_tokens, sample_tokens_ref
 from ..ops.attention import doc_position_ids, doc_range_from_segment_ids, key_range_from_mask
 from ..ops.kv_cache import KVCache
 from ..ops.quant import FORMATS as QUANT_FORMATS, check_quantized, clear_quantized_, quantize_params_
@@ -307,7 +308,8 @@ class CausalLM(nn.Module):
                  do_sample: bool = False, temperature: float = 1.0, top_k: int = 0, eos_token_id: int | None = None,
                  seed: int = 0, max_len: int | None = None, graph: bool = False,
                  logits_out: list | None = None, kv_dtype=None, cache_out: list | None = None,
-                 prefill_chunk: int | None = None, kv_ring: bool = False) -> torch.Tensor:
+                 prefill_chunk: int | None = None, kv_ring: bool = False, top_p: float = 1.0,
+                 sampler: str = "torch") -> torch.Tensor:
         """``input_ids [B, S0]`` continued by ``max_new_tokens`` = N tokens: int64 ``[B, S0 + N]``.  Greedy by
         default; ``do_sample``: temperature, then top-k (0 = the whole vocabulary), drawn with a
         ``torch.Generator`` seeded with ``seed``.  ``attention_mask``: a LEFT-padded batch (``prefill``).  After
@@ -315,8 +317,18 @@ class CausalLM(nn.Module):
         waits for the host.  ``max_len``: cache positions (default S0 + N; at most ``cfg.max_positions``).  The
         model is put in eval mode for the call and its mode is restored.
 
+        ``top_p`` < 1 (nucleus sampling) or ``sampler="device"``: ``do_sample`` follows the counter-based law of
+        ``ops.functional.sample_tokens_ref`` instead -- temperature, top-k, top-p, then a draw that is a pure
+        function of (``seed``, step, row) -- through ``ops.functional.sample_tokens``: one HIP kernel per step on
+        the GPU, end-of-sequence handling included, the reference on the CPU and the reference path.  The same
+        seed gives the same tokens on either wherever the logits agree.  With ``graph=True`` the captured region
+        is then ``decode_step``, the selection and the step counter: a replay feeds the next through the static
+        token buffer and no eager op runs between steps.  ``sampler="torch"`` with ``top_p`` = 1 (the default)
+        is the ``torch.Generator`` stream described above, unchanged.
+
         ``graph=True`` (GPU): after two eager steps ``decode_step`` is captured once into a HIP graph -- one
-        stream, the token a static input -- and replayed; the token selection stays outside the graph.
+        stream, the token a static input -- and replayed; with the torch sampler the token selection stays outside
+        the graph (with the device law it is inside: above).
         ``logits_out``: a list that receives each step's ``[B, V]`` logits (tests).
 
         ``kv_dtype``: ``"fp8"`` (or ``torch.float8_e4m3fn``) keeps the cache as e4m3fn codes with one fp32 scale per
@@ -348,6 +360,10 @@ class CausalLM(nn.Module):
             raise ValueError(f"generate: prompt {S0} + {N} new tokens exceed max_len = {max_len}")
         if do_sample and temperature <= 0:
             raise ValueError(f"temperature must be positive, got {temperature}")
+        if not 0.0 < top_p <= 1.0:
+            raise ValueError(f"top_p must lie in (0, 1], got {top_p}")
+        if sampler not in ("torch", "device"):
+            raise ValueError(f"sampler must be 'torch' or 'device', got {sampler!r}")
         w = self.head.weight
         dev = w.device
         input_ids = input_ids.to(dev)
@@ -363,6 +379,9 @@ class CausalLM(nn.Module):
         was_training = self.training
         self.eval()
         try:
+            if do_sample and (top_p < 1.0 or sampler == "device"):
+                return self._generate_law(input_ids, N, cache, attention_mask, prefill_chunk, temperature, top_k, top_p,
+                                          seed, eos_token_id, graph, logits_out)
             out = [input_ids.to(torch.int64)]
             done = torch.zeros(B, dtype=torch.bool, device=dev)
             logits = self._prefill_chunked(input_ids, cache, attention_mask, prefill_chunk) if N > 0 else None
@@ -397,6 +416,50 @@ class CausalLM(nn.Module):
             return torch.cat(out, 1)
         finally:
             self.train(was_training)
+
+    def _generate_law(self, input_ids, N, cache, attention_mask, prefill_chunk, temperature, top_k, top_p, seed, eos,
+                      graph, logits_out):
+        """``generate``'s steps with ``ops.functional.sample_tokens``: the tokens go into a ``[B, N]`` buffer at the
+        column the device step counter names, so a captured step (``decode_step`` + selection + counter) is complete."""
+        B, dev = input_ids.shape[0], input_ids.device
+        pad = self.cfg.pad_token_id
+        toks = torch.full((B, N), pad, dtype=torch.int64, device=dev)
+        step = torch.zeros(1, dtype=torch.int64, device=dev)
+        done = torch.zeros(B, dtype=torch.uint8, device=dev) if eos is not None else None
+
+        sample = sample_tokens if self.rt.use_fused(input_ids) else sample_tokens_ref
+
+        def select(logits, keep_logits=True):
+            if logits_out is not None and keep_logits:
+                logits_out.append(logits.clone())
+            tok = sample(logits, temperature, top_k, top_p, seed, step, done, eos, pad)
+            toks.scatter_(1, step.view(1, 1).expand(B, 1), tok.view(B, 1))
+            step.add_(1)
+            return tok
+
+        captured = None
+        if N > 0:
+            tok = select(self._prefill_chunked(input_ids, cache, attention_mask, prefill_chunk))
+        for t in range(N - 1):
+            if graph and t >= 2:
+                if captured is None:
+                    static_tok = tok.clone()
+                    torch.cuda.synchronize()
+                    captured = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(captured, capture_error_mode=CAPTURE_ERROR_MODE):
+                        static_logits = self.decode_step(static_tok, cache)
+                        static_tok.copy_(select(static_logits, keep_logits=False))
+                    cache.filled -= 1          # the capture computed nothing: only replays advance
+                captured.replay()
+                cache.filled += 1
+                if logits_out is not None:
+                    logits_out.append(static_logits.clone())
+            else:
+                tok = select(self.decode_step(tok, cache))
+        if captured is not None:
+            torch.cuda.synchronize()
+            captured.reset()
+        return torch.cat([input_ids.to(torch.int64), toks], 1)
 
     def _prefill_chunked(self, input_ids, cache, attention_mask, chunk):
         S0 = input_ids.shape[1]

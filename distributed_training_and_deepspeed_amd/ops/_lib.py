@@ -164,6 +164,8 @@ _SIGS = {
     # gemm_ln.hip
     "dtd_gemm_ln_supported": (I, [I, I, I, I, I, I, I]),
     "dtd_gemm_ln": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, F, P, U32, P]),
+    # sample.hip (dtype, logits, ld, B, V, 1 / temperature, top_k, top_p, seed, step, done or null, eos, pad, out)
+    "dtd_sample_tokens": (I, [I, P, L, I, I, F, I, ctypes.c_double, ctypes.c_uint64, P, P, L, L, P, P]),
     # reduce.hip
     "dtd_splitk_reduce": (I, [P, I, I, ctypes.c_longlong, P, I, I, P]),
 }

@@ -1137,3 +1137,122 @@ class Softmax(torch.nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return _SoftmaxFn.apply(x)
+
+
+# --------------------------------------------------------------------------------------
+# token sampling: temperature, top-k, top-p and the draw (ops/csrc/sample.hip)
+# --------------------------------------------------------------------------------------
+SAMPLE_SID = 0x53414D50      # the sampler's RNG stream; RngState.sid() stays below 2^30
+SAMPLE_MAX_VOCAB = 1 << 20   # sample.hip kMaxV
+SAMPLE_FRAC_BITS = 40        # sample.hip kFrac: a mass is rounded to 2^-40 of the row's largest
+
+
+def _check_sampling(logits, temperature, top_p, done, eos, pad):
+    if logits.dim() != 2 or logits.shape[1] < 1:
+        raise ValueError(f"sample_tokens takes logits [B, V], got {tuple(logits.shape)}")
+    if not temperature > 0:
+        raise ValueError(f"temperature must be positive, got {temperature}")
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"top_p must lie in (0, 1], got {top_p}")
+    if done is not None:
+        if eos is None or pad is None:
+            raise ValueError("sample_tokens: done needs eos and pad")
+        if done.shape != logits.shape[:1] or done.dtype not in (torch.uint8, torch.bool) or done.device != logits.device:
+            raise ValueError("sample_tokens: done must be a uint8 (or bool) [B] tensor on the logits' device")
+
+
+def sample_uniform24(seed: int, step: int, rows: int) -> torch.Tensor:
+    """The 24-bit draws of rows 0 .. rows-1 (int64; u = value / 2^24): the counter hash of ``ops/rng.py`` on the
+    stream ``SAMPLE_SID``, bit for bit what ``sample.hip`` computes."""
+    from .rng import M32, _keys, _mix32
+    k0, k1 = _keys(int(seed) & 0x7FFFFFFFFFFFFFFF, int(step), SAMPLE_SID)
+    b = torch.arange(rows, dtype=torch.int64)
+    return _mix32(((b ^ k0) + k1) & M32) >> 8
+
+
+def sample_keep_ref(logits: torch.Tensor, temperature: float, top_k: int, top_p: float):
+    """The kept set of the sampling law: ``(keep, mass, margin)`` -- bool ``[B, V]``, the fp64 masses
+    ``exp(z - max z)`` of every entry, and the fp64 ``[B]`` distance of ``top_p Z`` from the nearest cumulative
+    mass of the descending order (inf without top-p), in units of the row's largest mass."""
+    B, V = logits.shape
+    dev = logits.device
+    inv_t = float(torch.tensor(1.0 / temperature, dtype=torch.float32))
+    z = logits.float() * inv_t
+    valid = z > float("-inf")
+    z = torch.where(valid, z, torch.full_like(z, float("-inf")))
+    order = torch.sort(z, dim=-1, descending=True, stable=True).indices      # ties: the lower index first
+    keep_s = valid.gather(1, order)
+    if 0 < top_k < V:
+        keep_s = keep_s & (torch.arange(V, device=dev) < top_k)
+    m = z.max(-1, keepdim=True).values
+    mass = torch.exp(z.double() - torch.where(torch.isfinite(m), m, torch.zeros_like(m)).double())
+    margin = torch.full((B,), float("inf"), dtype=torch.float64, device=dev)
+    if top_p < 1.0:
+        e_s = mass.gather(1, order) * keep_s
+        cum = e_s.cumsum(-1)
+        cut = top_p * cum[:, -1:]
+        keep_s = keep_s & (cum - e_s < cut)              # the shortest prefix that reaches top_p
+        margin = (cum - cut).abs().min(-1).values
+    return torch.zeros_like(keep_s).scatter_(1, order, keep_s), mass, margin
+
+
+def sample_tokens_ref(logits: torch.Tensor, temperature: float, top_k: int, top_p: float, seed: int, step,
+                      done: torch.Tensor | None = None, eos: int | None = None, pad: int | None = None,
+                      check: bool = False, return_margin: bool = False):
+    """The sampling law in plain PyTorch (masses in fp64); int64 ``[B]``.
+
+    ``z = float32(logits) * float32(1 / temperature)``; a ``-inf`` (or NaN) entry is never kept.  top-k
+    (0 or ``>= V``: off) keeps the k largest z, a tie going to the lower index.  top-p (1: off; HF's
+    ``TopPLogitsWarper`` with ``min_tokens_to_keep = 1``) orders those by z descending, ties by the lower
+    index, and keeps the shortest prefix whose softmax mass reaches ``top_p``.  The draw: ``u`` in [0, 1) is
+    ``sample_uniform24(seed, step, B)[b] / 2^24`` and the token is the first kept index, in ascending index
+    order, whose running mass exceeds ``u Z``, Z the kept mass.  ``step``: an int or an int64 ``[1]`` tensor.
+    A row without a finite logit gives 0 (``check``: a ``ValueError``).  ``done`` (uint8 or bool ``[B]``,
+    updated in place) with ``eos`` and ``pad``: a finished row emits ``pad``; a row that emits ``eos`` is finished.
+
+    ``return_margin``: also the fp64 ``[B]`` distance of each row from a different outcome -- of ``u Z`` from
+    the nearest boundary of the kept CDF, and ``sample_keep_ref``'s for ``top_p`` -- in units of the row's
+    largest mass, of which the kernel's masses are fixed-point fractions."""
+    _check_sampling(logits, temperature, top_p, done, eos, pad)
+    B, V = logits.shape
+    keep, mass, margin = sample_keep_ref(logits, temperature, top_k, top_p)
+    if check and not bool(keep.any(-1).all()):
+        raise ValueError("sample_tokens: a row has no finite logit")
+    cdf = (mass * keep).cumsum(-1)                       # in index order: the law needs no sort for the draw
+    step_i = int(step.item()) if isinstance(step, torch.Tensor) else int(step)
+    u = sample_uniform24(seed, step_i, B).to(logits.device).double().view(B, 1) / float(1 << 24)
+    t = u * cdf[:, -1:]
+    tok = (cdf <= t).sum(-1).clamp_(max=V - 1)
+    tok = torch.where(keep.any(-1), tok, torch.zeros_like(tok))
+    if done is not None:
+        tok = torch.where(done.bool(), torch.full_like(tok, pad), tok)
+        done |= (tok == eos).to(done.dtype)
+    if return_margin:
+        return tok, torch.minimum(margin, (cdf - t).abs().min(-1).values)
+    return tok
+
+
+def sample_tokens(logits: torch.Tensor, temperature: float, top_k: int, top_p: float, seed: int, step: torch.Tensor,
+                  done: torch.Tensor | None = None, eos: int | None = None, pad: int | None = None) -> torch.Tensor:
+    """One token per row of ``logits [B, V]`` by the law of ``sample_tokens_ref``: int64 ``[B]``.  CUDA bf16 /
+    fp32 logits take the HIP kernel -- one launch, no host synchronisation, graph-capturable: ``step`` is a
+    device int64 ``[1]`` counter the caller advances, ``done`` is updated on the device.  Anything else takes
+    the reference, which reads ``step`` back to the host (a synchronisation; not capturable): that covers the
+    CPU and CUDA logits of another dtype.  The kernel's masses are fixed-point (``SAMPLE_FRAC_BITS``): it returns the reference's
+    token unless ``u`` or ``top_p`` lies within ``V 2^-40`` (``return_margin``'s unit) of a boundary."""
+    if not (logits.is_cuda and logits.dtype in (torch.bfloat16, torch.float32)):
+        return sample_tokens_ref(logits, temperature, top_k, top_p, seed, step, done, eos, pad)
+    _check_sampling(logits, temperature, top_p, done, eos, pad)
+    B, V = logits.shape
+    if V > SAMPLE_MAX_VOCAB:
+        raise ValueError(f"sample_tokens: V = {V} exceeds {SAMPLE_MAX_VOCAB}")
+    if not (isinstance(step, torch.Tensor) and step.dtype == torch.int64 and step.numel() == 1 and step.is_cuda):
+        raise ValueError("sample_tokens: step must be an int64 [1] tensor on the device")
+    if logits.stride(1) != 1:
+        logits = logits.contiguous()
+    inv_t = float(torch.tensor(1.0 / temperature, dtype=torch.float32))
+    out = torch.empty(B, dtype=torch.int64, device=logits.device)
+    _lib.call("dtd_sample_tokens", _lib.dt(logits), logits.data_ptr(), logits.stride(0), B, V, inv_t,
+              max(int(top_k), 0), float(top_p), int(seed) & 0x7FFFFFFFFFFFFFFF, step.data_ptr(), _lib.ptr(done),
+              0 if eos is None else int(eos), 0 if pad is None else int(pad), out.data_ptr(), _lib.stream())
+    return out

@@ -1,7 +1,8 @@
 """Text generation with a KV cache for the Llama family (random-init weights, synthetic prompts).
 
     python generate_text.py --model-name llama-tiny-gqa --batch-size 4 --prompt-len 64 --max-new-tokens 64 \
-        [--graph] [--impl auto|fused|reference] [--sample --top-k 50 --temperature 0.8] [--metrics-json F] \
+        [--graph] [--impl auto|fused|reference] [--sample --top-k 50 --temperature 0.8 --top-p 0.9 --sampler device] \
+        [--metrics-json F] \
         [--kv-cache-dtype auto|fp8] [--kv-ring]
 
 Prints the token ids of row 0, the prefill time and the decode rate.  The prompt goes through the model once
@@ -38,6 +39,10 @@ def main(argv=None):
     ap.add_argument("--sample", action="store_true")
     ap.add_argument("--top-k", type=int, default=0)
     ap.add_argument("--temperature", type=float, default=1.0)
+    ap.add_argument("--top-p", type=float, default=1.0, help="nucleus sampling (with --sample); below 1 it takes the device law")
+    ap.add_argument("--sampler", default="torch", choices=("torch", "device"),
+                    help="device: the counter-based sampling law (ops.functional.sample_tokens; one HIP kernel per step, "
+                         "inside the graph with --graph); torch: torch.multinomial with a seeded generator")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default=None, help="default: cuda:0 when there is a GPU, else cpu")
     ap.add_argument("--dtype", default=None, choices=("bfloat16", "float32"), help="default: bfloat16 on the GPU")
@@ -72,7 +77,7 @@ def main(argv=None):
     ids = torch.randint(3, cfg.vocab_size, (B, S0), generator=torch.Generator().manual_seed(args.seed)).to(dev)
     kw = dict(do_sample=args.sample, temperature=args.temperature, top_k=args.top_k, seed=args.seed, graph=args.graph,
               kv_dtype=None if args.kv_cache_dtype == "auto" else args.kv_cache_dtype, prefill_chunk=args.prefill_chunk,
-              kv_ring=args.kv_ring)
+              kv_ring=args.kv_ring, top_p=args.top_p, sampler=args.sampler)
 
     def timed(n):
         _sync(dev)

@@ -11,6 +11,11 @@ the argmax of the last position.  Each arm is timed twice, interleaved; the whol
 ``--weight-dtype fp8`` / ``mxfp4`` quantises the projections first (``quantize_weights_``: the decode steps stream the codes),
 ``--skinny-gemm`` sends the bf16 products of at most 64 rows to ``gemm_skinny.hip``.
 
+``--sampler`` times the sampled step instead (``do_sample``, ``top_k=50``, ``graph=True``): ``sampler="torch"``
+(eager ``topk`` / ``softmax`` / ``multinomial`` between replays) against ``sampler="device"`` (``sample.hip`` inside the
+graph), the arms alternating, two repeats; then the selection alone at V = 32000 and 128256, the kernel against the
+torch sequence, in ms per call of a 200-call loop.  Default --out then: profiles/generate_sampler.jsonl.
+
 One JSON line per (model, B), appended to --out.
 
 Usage: python scripts/bench_generate.py [--out profiles/generate.jsonl] [--models llama-160m,tinyllama-1.1b]
@@ -96,6 +101,58 @@ def prompt_pass(model, args, iters=10):
         emit(args.out, rec)
 
 
+@torch.no_grad()
+def sampler_steps(model, args):
+    """ms per sampled step, torch sampler against device sampler, both with ``graph=True``."""
+    steps = NEW - SHORT
+    for B in (int(b) for b in args.batches.split(",")):
+        prompt = torch.randint(3, model.cfg.vocab_size, (B, PROMPT), generator=torch.Generator().manual_seed(B)).cuda()
+        arms = {s: (lambda n, s=s: model.generate(prompt, n, do_sample=True, temperature=0.8, top_k=50, seed=1, graph=True,
+                                                  sampler=s)) for s in ("torch", "device")}
+        for fn in arms.values():
+            fn(SHORT)
+        runs = {k: [] for k in arms}
+        for _ in range(2):
+            for key, fn in arms.items():
+                t_long, t_short = wall(lambda: fn(NEW))[1], wall(lambda: fn(SHORT))[1]
+                runs[key].append((t_long - t_short) / steps * 1e3)
+        rec = {"case": "sampled_step", "model": model.cfg.name, "B": B, "V": model.cfg.vocab_size, "prompt": PROMPT,
+               "new_tokens": NEW, "top_k": 50, "graph": True, "steps_timed": steps}
+        for key, r in runs.items():
+            rec[f"{key}_ms_per_step"] = round(sum(r) / 2, 4)
+            rec[f"{key}_runs_ms_per_step"] = [round(x, 4) for x in r]
+        rec["torch_over_device"] = round(rec["torch_ms_per_step"] / rec["device_ms_per_step"], 3)
+        emit(args.out, rec)
+
+
+@torch.no_grad()
+def sampler_alone(args, calls=200):
+    """The selection alone, eager launches from Python: the kernel against ``CausalLM._select``'s torch sequence."""
+    from distributed_training_and_deepspeed_amd.models.causal_lm import CausalLM
+    from distributed_training_and_deepspeed_amd.ops.functional import sample_tokens
+    step = torch.zeros(1, dtype=torch.int64, device="cuda")
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    for V in (32000, 128256):
+        for B in (int(b) for b in args.batches.split(",")):
+            logits = (torch.randn(B, V, generator=torch.Generator().manual_seed(V)) * 3).bfloat16().cuda()
+            for top_k, top_p in ((50, 1.0), (50, 0.9), (0, 0.9), (0, 1.0)):
+                arms = {"device": lambda: sample_tokens(logits, 0.8, top_k, top_p, 1, step)}
+                if top_p == 1.0:
+                    arms["torch"] = lambda: CausalLM._select(logits, True, 0.8, top_k, gen)
+                runs = {k: [] for k in arms}
+                for fn in arms.values():
+                    fn()
+                for _ in range(2):
+                    for key, fn in arms.items():
+                        runs[key].append(wall(lambda: [fn() for _ in range(calls)])[1] / calls * 1e3)
+                rec = {"case": "selection_alone", "V": V, "B": B, "dtype": "bfloat16", "top_k": top_k, "top_p": top_p,
+                       "calls": calls}
+                for key, r in runs.items():
+                    rec[f"{key}_ms"] = round(sum(r) / 2, 4)
+                    rec[f"{key}_runs_ms"] = [round(x, 4) for x in r]
+                emit(args.out, rec)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", type=str, default="")
@@ -111,9 +168,15 @@ def main():
                          "the arms with and without FP8 activations alternate in one process")
     ap.add_argument("--skinny-gemm", action="store_true", help="bf16 products of at most 64 rows on gemm_skinny.hip")
     ap.add_argument("--skip-recompute", action="store_true", help="leave the no-cache baseline out")
+    ap.add_argument("--sampler", action="store_true",
+                    help="time the sampled step, torch sampler against device sampler, and the selection alone")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_generate.py needs a GPU")
+    if args.sampler and args.prompt_pass:
+        raise SystemExit("--sampler and --prompt-pass are separate measurements: give one")
+    if args.sampler and not args.out:
+        args.out = os.path.join(ROOT, "profiles", "generate_sampler.jsonl")
     steps = NEW - SHORT
     kv_dtype = None if args.kv_cache_dtype == "auto" else args.kv_cache_dtype
     for name in args.models.split(","):
@@ -121,8 +184,11 @@ def main():
         if args.weight_dtype != "auto":
             model.quantize_weights_(args.weight_dtype)
         G.set_skinny(args.skinny_gemm)
-        if args.prompt_pass:
+        if args.sampler:
+            sampler_steps(model, args)
+        elif args.prompt_pass:
             prompt_pass(model, args)
+        if args.sampler or args.prompt_pass:
             del model
             torch.cuda.empty_cache()
             continue
@@ -168,6 +234,8 @@ def main():
             emit(args.out, rec)
         del model
         torch.cuda.empty_cache()
+    if args.sampler:
+        sampler_alone(args)
 
 
 if __name__ == "__main__":
